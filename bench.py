@@ -30,7 +30,14 @@ Headline workload by GPU count (BASELINE.json configs):
 value = total edges*K processed by all ranks / max-over-ranks wall time, where
 edges = nnz of the off-diagonal L_hat (= symmetrised adjacency without loops).
 
-Also printed in the same JSON line:
+A plain run sets up, warms up, times --steps steps (ms_per_step = the wall
+time of one of them), writes the last timed step's H and S with
+--dump-outputs DIR, and prints the line.  Everything below is measured only
+with --full (at N > 1 also: the exchange comparison, the checks, the replicas
+and the one-GPU run of the same config; a plain N > 1 run times the first
+--exchange kind only).
+
+With --full, also in the same JSON line:
   roofline      -- SURVEY.md 8(d)'s algorithmic bytes per launch (B_step =
                    8 nnz + 4 (N+1) + 20 N F over the launched rows) / the step
                    kernel's mean duration from HIP events recorded live around
@@ -77,6 +84,16 @@ def parse():
     ap.add_argument("--F", type=int, default=None)
     ap.add_argument("--s", type=float, default=0.8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the roofline (a second, "
+                         "profiled run of the steps), prologue, cold and F=1 figures, the CPU baseline and its parity "
+                         "check, the companion workloads, the row-sharded extras and, at N > 1, the exchange "
+                         "comparison, checks, replicas and the one-GPU run of the same config.  Without it a run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (H and S as the caller "
+                         "receives them) to DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded sample "
+                         "of the rows of a larger output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
     ap.add_argument("--traffic-json", default="auto",
@@ -220,6 +237,23 @@ def _rel_err(got, ref) -> float:
     return float((err[ok] / scale[ok]).max()) if ok.any() else float(err.max(initial=0.0))
 
 
+DUMP_BUDGET = 64_000_000   # bytes, over all the arrays of one --dump-outputs
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array as directory/<name>.npy, float32.  An array
+    over its share of the budget is cut to a fixed, seeded sample of its rows
+    (the same rows in every run with the same arguments)."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays)) - 4096   # the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(np.asarray(a, np.float32))
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], share // row_bytes, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- row-sharded runs
 _GRAPHS: dict = {}
 
@@ -260,7 +294,8 @@ def shared_graph(config, seed, world, rank, device):
 
 
 def run_sharded(config, K, F, steps, warmup, seed, s_heat, world, rank, device, exchange="rccl",
-                median_reps: int = 0, check: bool = True, min_time: float = 0.0):
+                median_reps: int = 0, check: bool = True, min_time: float = 0.0, dump=None,
+                attribution: bool = True):
     """One graph (generated identically on every rank, on the GPU) split into
     nnz-balanced row blocks; per Chebyshev step one halo exchange (`exchange`:
     RCCL send/recv or IPC pull in the native chain, or torch
@@ -322,13 +357,16 @@ def run_sharded(config, K, F, steps, warmup, seed, s_heat, world, rank, device, 
         dist.barrier()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
+    last = None
     for _ in range(steps):
-        run()
+        last = run()
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     _log(f"sharded {config} ({exchange}): timed {steps} chains in {elapsed:.3f} s")
+    if dump and rank == 0 and last is not None:   # rank 0's rows of the last timed chain's (H, S)
+        dump_outputs(dump, {"H": last[0].cpu().numpy(), "S": last[1].cpu().numpy()})
     med = None
     if median_reps > 0:   # per-chain times (HIP events on the launch stream), median over ranks' max
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(median_reps + 1)]
@@ -345,9 +383,11 @@ def run_sharded(config, K, F, steps, warmup, seed, s_heat, world, rank, device, 
             med = _allreduce(med, dist.ReduceOp.MAX, device)
     # kernel / exchange attribution: one more pass, eager, with HIP events (outside the timed region)
     dinfo = sw.info()   # after the timed chains: was the chain replayed as a hipGraph?
-    sw.profile_start()
-    run()
-    prof = sw.profile_collect()
+    prof = None
+    if attribution:
+        sw.profile_start()
+        run()
+        prof = sw.profile_collect()
     chk = None
     if check:
         chk = _check_vs_unsharded(sw, indptr_d, indices_d, n_t, r0, r1, F, K, s_heat, world, device,
@@ -375,7 +415,7 @@ def run_sharded(config, K, F, steps, warmup, seed, s_heat, world, rank, device, 
         else:
             kernel = ("hybrid step: cheb_tiles_kernel + tiles_combine_kernel + the tail on the step kernel "
                       f"(forms run: {forms[-1] if forms else 'unknown'}; rank 0 shard)")
-    avg_ms = prof["step_ms"]
+    avg_ms = prof["step_ms"] if prof else None
     sw.close()
     del sw
     torch.cuda.empty_cache()
@@ -412,8 +452,8 @@ def run_sharded(config, K, F, steps, warmup, seed, s_heat, world, rank, device, 
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": (b_step / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if avg_ms else None,
                      "traffic": None, "kernel": kernel,
-                     "algorithmic_bytes_per_launch": b_step, "avg_launch_us": avg_ms * 1e3,
-                     "avg_exchange_us": prof["exchange_ms"] * 1e3,
+                     "algorithmic_bytes_per_launch": b_step, "avg_launch_us": avg_ms * 1e3 if prof else None,
+                     "avg_exchange_us": prof["exchange_ms"] * 1e3 if prof else None,
                      "graph_replayed": bool(dinfo.get("captured")) if dinfo else None,
                      "byte_model": _byte_model(lds_info),
                      "lds_plan": lds_info,
@@ -600,16 +640,18 @@ def prologue_timing(g, L, device, reps: int = 5) -> dict:
                     "time around a device sync, median; not in the chain's time (SURVEY 8(d))"}
 
 
-def single_gpu_line(args, g, config, K, F, world, rank, device, full=True):
+def single_gpu_line(args, g, config, K, F, world, rank, device, full=True, dump=None):
     """One graph per rank (no collective): graph_wavelet_features passes timed
     as the driver's contract says.  full=False: value / step / roofline only
-    (companion lines)."""
+    (companion lines).  Without --full: the value and ms_per_step only.
+    dump: the --dump-outputs directory (the last timed pass's H and S)."""
     import wats_hip
     st = g.stats()
     unit = g.values is None or bool(np.all(g.values == 1))   # the value-free Clenshaw chain applies
     L = wats_hip.NormalizedLaplacian.from_graph(g, device=device)
     if getattr(args, "tune", None):
         L.tune(**args.tune)
+    full = full and args.full
     pro = prologue_timing(g, L, device) if (full and world == 1) else None
     rng = np.random.default_rng(1 + rank)
     if F == 1:
@@ -672,14 +714,44 @@ def single_gpu_line(args, g, config, K, F, world, rank, device, full=True):
     # the same K passes again, with events around every step launch and pass
     elapsed, _, _ = timed(False)
     S_host = S.cpu().numpy() if (full and world == 1) else None   # the benchmarked pass's S (parity check)
-    elapsed_prof, prof, median_ms = timed(True)
+    if dump and rank == 0:
+        dump_outputs(dump, {"H": H.cpu().numpy(), "S": S.cpu().numpy() if S_host is None else S_host})
     _log(f"{config}: timed {args.steps} passes in {elapsed:.3f} s")
-    cold = cold_chains(step, L, args.cold_reps, device) if (full and args.cold_reps > 0) else None
-    f1 = f1_companion(lib, L, K, args.s, args.steps, device, unit) if (full and args.f1_companion and F > 1) else None
     edges_k = float(nnz) * K * args.steps
     if world > 1:
         elapsed = _allreduce(elapsed, dist.ReduceOp.MAX, device)
         edges_k = _allreduce(edges_k, dist.ReduceOp.SUM, device)
+    line = {
+        "metric": f"Chebyshev SpMM-chain edges*K/s ({config}-size, K={K}) + %HBM roofline",
+        "value": edges_k / elapsed,
+        "unit": "edges*K/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "settle_s": args.settle_s,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{config}-size R-MAT graph (a=.57,b=c=.19), symmetrised, no self loops; "
+                        f"graph_wavelet_features K={K}, F={F} "
+                        f"{'log1p-degree signal' if F == 1 else 'randn signal columns'}, s={args.s}",
+            "N": n, "nnz": nnz, "isolated": st["isolated"], "max_degree": st["max_degree"],
+            "K": K, "F": F, "per_rank": "one graph per rank, no collective",
+            "parallelism": f"graphs x{world}",
+        },
+    }
+    if not args.full:   # a plain run: the headline figure only (the roofline takes a profiled run of its own)
+        L.close()
+        del S, H, X
+        torch.cuda.empty_cache()
+        return line
+    elapsed_prof, prof, median_ms = timed(True)
+    cold = cold_chains(step, L, args.cold_reps, device) if (full and args.cold_reps > 0) else None
+    f1 = f1_companion(lib, L, K, args.s, args.steps, device, unit) if (full and args.f1_companion and F > 1) else None
     avg_ms = prof["sum_ms"] / max(1, prof["launches"])
     # the folded chain (tuning key fold): each pass's first launch is
     # cheb_team4_first_kernel, which also does the former permute-in pass's work; the roofline is
@@ -719,28 +791,7 @@ def single_gpu_line(args, g, config, K, F, world, rank, device, full=True):
     if tj and tj != "none" and os.path.exists(tj):
         traffic = json.load(open(tj)).get("bytes_per_launch")
         traffic_src = os.path.relpath(tj, REPO) if os.path.isabs(tj) else tj
-    line = {
-        "metric": f"Chebyshev SpMM-chain edges*K/s ({config}-size, K={K}) + %HBM roofline",
-        "value": edges_k / elapsed,
-        "unit": "edges*K/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "settle_s": args.settle_s,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{config}-size R-MAT graph (a=.57,b=c=.19), symmetrised, no self loops; "
-                        f"graph_wavelet_features K={K}, F={F} "
-                        f"{'log1p-degree signal' if F == 1 else 'randn signal columns'}, s={args.s}",
-            "N": n, "nnz": nnz, "isolated": st["isolated"], "max_degree": st["max_degree"],
-            "K": K, "F": F, "per_rank": "one graph per rank, no collective",
-            "parallelism": f"graphs x{world}",
-        },
+    line.update({
         "roofline": {
             "bound": "hbm",
             "achieved": achieved,
@@ -791,7 +842,7 @@ def single_gpu_line(args, g, config, K, F, world, rank, device, full=True):
                   "passes timed right after with HIP events around every step-kernel launch and every pass "
                   "(ms_per_step_profiled, median_step_ms_profiled; value_median = nnz*K / that median)",
         "edges_K_F_per_s": edges_k * F / elapsed,
-    }
+    })
     if pro is not None:
         line["prologue"] = pro
     if cold is not None:
@@ -826,6 +877,8 @@ def _companion_summary(d: dict) -> dict:
 # ----------------------------------------------------------------------------- main
 def main():
     args = parse()
+    if not args.full:   # a plain run: the headline only
+        args.sharded_extra, args.replicas, args.pick_exchange = "none", 0, 0
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -868,13 +921,16 @@ def main():
                        "error": f"the row-sharded headline did not finish within {args.headline_timeout:.0f} s"},
                       args.out)
             os._exit(3)
+        # per-chain medians, the kernel / exchange attribution pass and the check against the unsharded chain
+        # are runs of their own: --full
+        hk = dict(median_reps=max(20, args.steps) if args.full else 0, check=args.full, attribution=args.full)
         hw = threading.Timer(args.headline_timeout, _expire_headline)
         hw.daemon = True
         hw.start()
         exc = None
         try:
             line = run_sharded(cfg, args.K, args.F, args.steps, args.warmup, args.seed, args.s, world, rank, device,
-                               exchanges[0], median_reps=max(20, args.steps))
+                               exchanges[0], dump=args.dump_outputs, **hk)
         except Exception as e:  # noqa: BLE001 -- keep a headline: the next exchange, noted in the line
             exc = e
         if _any_rank(exc is not None, world):   # every rank switches together, or none does
@@ -885,7 +941,7 @@ def main():
             _log(f"headline with exchange {exchanges[0]} failed ({type(exc).__name__}: {exc}); using {exchanges[1]}")
             torch.cuda.empty_cache()
             line = run_sharded(cfg, args.K, args.F, args.steps, args.warmup, args.seed, args.s, world, rank, device,
-                               exchanges[1], median_reps=max(20, args.steps))
+                               exchanges[1], dump=args.dump_outputs, **hk)
             line["headline_fallback"] = f"exchange {exchanges[0]} failed: {type(exc).__name__}: {exc}"
             exchanges = exchanges[1:] + exchanges[:1]
         hw.cancel()
@@ -937,11 +993,17 @@ def main():
                                  "grouped send/recv whose check passed, exchange_compare); the N = 1 line carries "
                                  "the same run at one rank as `sharded`; same_config_1gpu: the same config "
                                  "unsharded on one GPU")
+        if not args.full:
+            line["headline_note"] = ("N > 1 headline: BASELINE.json configs[3] (Reddit-size, 1-D row-sharded, halo "
+                                     f"exchange '{line['config'].get('exchange')}', the first --exchange kind); "
+                                     "--full also times the second kind and reports the faster one whose check "
+                                     "passed, with the checks, replicas and the same config on one GPU")
         try:
-            torch.cuda.empty_cache()
-            line["same_config_1gpu"] = one_gpu_chain(cfg, args.K, args.F, args.steps, args.seed, args.s, device,
-                                                     world, rank)
-            line["same_config_1gpu"]["speedup"] = line["value"] / line["same_config_1gpu"]["value"]
+            if args.full:
+                torch.cuda.empty_cache()
+                line["same_config_1gpu"] = one_gpu_chain(cfg, args.K, args.F, args.steps, args.seed, args.s, device,
+                                                         world, rank)
+                line["same_config_1gpu"]["speedup"] = line["value"] / line["same_config_1gpu"]["value"]
         except Exception as exc:  # noqa: BLE001
             line["same_config_1gpu"] = {"error": f"{type(exc).__name__}: {exc}"}
     else:
@@ -949,8 +1011,8 @@ def main():
         K = args.K if args.K is not None else K_def
         F = args.F if args.F is not None else F_def
         g = named_graph(args.config, seed=args.seed + rank)   # independent graph per rank
-        line = single_gpu_line(args, g, args.config, K, F, world, rank, device, full=True)
-        if world == 1 and args.connected_companion and args.config == "ogbn-arxiv":
+        line = single_gpu_line(args, g, args.config, K, F, world, rank, device, full=True, dump=args.dump_outputs)
+        if args.full and world == 1 and args.connected_companion and args.config == "ogbn-arxiv":
             a = argparse.Namespace(**vars(args))
             a.cold_reps = 0
             line["connected_companion"] = _companion_summary(
@@ -959,7 +1021,7 @@ def main():
             line["connected_companion"]["what"] = ("the same R-MAT graph with every isolated node attached to one "
                                                    "random node (graphgen.connect_isolated): no closed-form rows, "
                                                    "as the real ogbn-arxiv")
-        if world == 1 and args.pubmed_companion and args.config == "ogbn-arxiv":
+        if args.full and world == 1 and args.pubmed_companion and args.config == "ogbn-arxiv":
             # BASELINE.json configs[1]: the small, launch-bound chain (replayed as a hipGraph)
             a = argparse.Namespace(**vars(args))
             a.cold_reps = 0
@@ -1030,7 +1092,7 @@ def main():
                                            device, x, min_time=0.2)
             except Exception as exc:  # noqa: BLE001
                 results[key] = {"error": f"{type(exc).__name__}: {exc}", "exchange": x}
-    if mode == "sharded" and len(exchanges) > 1:
+    if args.full and mode == "sharded" and len(exchanges) > 1:
         # the headline config with the other exchanges (same line, for the exchange comparison)
         cfg = args.scale_config if args.mode == "auto" else args.config
         if picked_other is not None:   # the exchange the headline did not pick, timed in full

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 WATS_BENCH_DEVICE=0 WATS_BENCH_PG=gloo timeout -k 10 ${TLIM:-500} python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port ${PORT:-29533} bench.py --gpus "$N" \
+    --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port ${PORT:-29533} bench.py --gpus "$N" --full \
     --steps ${STEPS:-5} --warmup 1 --exchange ${EXCH:-ipc} --sharded-extra "${EXTRA:-none}" \
     --out "$OUT/bench$N.json" > "$OUT/rehearse$N.log" 2>&1
 rc=$?

@@ -5,7 +5,7 @@
 #   smoke          __graft_entry__.smoke()
 #   tests          pytest -m gpu, every file but the full-size one
 #   fullsize       pytest tests/test_fullsize.py -m gpu
-#   bench          python bench.py (the driver's default N = 1 line) -> bench.json
+#   bench          python bench.py --full (the N = 1 line with everything beside the headline) -> bench.json
 #   headline_prof  rocprofv3 --kernel-trace --stats of the N = 1 headline workload ALONE
 #                  (no companions / extras): its kernel summary reproduces the line's roofline
 #   pmc            FETCH_SIZE / WRITE_SIZE / L2 hit passes of the headline alone -> traffic.json
@@ -18,7 +18,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${SESSION:-session}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-HEADLINE="--no-cpu-baseline --sharded-extra none --cold-reps 0 --f1-companion 0 --connected-companion 0 --pubmed-companion 0"
+HEADLINE="--full --no-cpu-baseline --sharded-extra none --cold-reps 0 --f1-companion 0 --connected-companion 0 --pubmed-companion 0"
 n=0
 stop_if_fatal() {  # $1 = rc, $2 = step
   echo "[$2] rc=$1 $(date +%T)" | tee -a "$OUT/steps.log"
@@ -39,7 +39,7 @@ for step in "$@"; do
           -p no:cacheprovider -rf > "$OUT/gpu_fullsize.log" 2>&1
       stop_if_fatal $? fullsize ;;
     bench)
-      timeout -k 10 600 python -u bench.py --steps ${STEPS:-20} --warmup 3 --out "$OUT/bench.json" > "$OUT/bench.log" 2>&1
+      timeout -k 10 600 python -u bench.py --full --steps ${STEPS:-20} --warmup 3 --out "$OUT/bench.json" > "$OUT/bench.log" 2>&1
       stop_if_fatal $? bench ;;
     headline_prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$$ -o run -- \
