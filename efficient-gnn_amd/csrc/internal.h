@@ -351,6 +351,7 @@ struct wg_laplacian_s {
   int device = 0;
   int64_t n_rows = 0, n_cols = 0, nnz_input = 0, nnz = 0, n_iso = 0, max_row = 0;
   bool reordered = true;
+  bool caller_ties = false;   // WG_FLAG_CALLER_TIES: rows of one length stay in caller order (prologue.hip)
   int32_t* rowptr = nullptr;  // internal order, int32
   int32_t* col = nullptr;
   float* val = nullptr;

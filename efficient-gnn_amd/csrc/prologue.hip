@@ -118,6 +118,41 @@ __global__ void sort_key_kernel(int64_t n, const int32_t* __restrict__ len, cons
   key[i] = ((unsigned long long)len[i] << 1) | (pure ? 0ull : 1ull);
 }
 
+// Tie key of the relabelling: wave per caller row, the two smallest rank0 (position
+// under the degree sort alone, iperm0) among the row's off-diagonal columns -- its hottest and
+// second-hottest neighbour -- as (first << 32) | second; rows with fewer neighbours fill up with
+// n_rows.  Rows of one length that gather the same hot rows then sit next to each other: they
+// share a wave, and the rows they are gathered from share cache lines.
+__global__ __launch_bounds__(kBlock) void tie_key_kernel(int64_t n_rows, const int64_t* __restrict__ indptr,
+                                                         const int32_t* __restrict__ indices,
+                                                         const int32_t* __restrict__ iperm0,
+                                                         unsigned long long* __restrict__ tie) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= n_rows) return;
+  const int32_t none = (int32_t)n_rows;
+  int32_t m1 = none, m2 = none;
+  for (int64_t e = indptr[row] + lane; e < indptr[row + 1]; e += 64) {
+    const int32_t c = indices[e];
+    if (c == row) continue;
+    const int32_t r = iperm0[c];
+    m2 = min(m2, max(m1, r));
+    m1 = min(m1, r);
+  }
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int32_t o1 = __shfl_down(m1, off, 64), o2 = __shfl_down(m2, off, 64);
+    m2 = min(max(m1, o1), min(m2, o2));
+    m1 = min(m1, o1);
+  }
+  if (lane == 0) tie[row] = ((unsigned long long)(uint32_t)m1 << 32) | (unsigned long long)(uint32_t)m2;
+}
+
+__global__ void gather_key_kernel(int64_t n, const int32_t* __restrict__ ids, const unsigned long long* __restrict__ key,
+                                  unsigned long long* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = key[ids[i]];
+}
+
 __global__ void count_pure_kernel(int64_t n, const unsigned long long* __restrict__ key, unsigned int* __restrict__ cnt) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && key[i] == 0ull) atomicAdd(cnt, 1u);
@@ -393,7 +428,8 @@ int build_operator(wg_laplacian_s* L, const int64_t* indptr, const int32_t* indi
     return WG_OK;
   }
   L->n_active = n_rows;
-  // relabelling by descending off-diagonal length (stable: ties keep caller order)
+  // relabelling by descending off-diagonal length (stable sorts; ties by neighbour, below, or in
+  // caller order)
   hipLaunchKernelGGL(iota_kernel, dim3(nb_rows), dim3(256), 0, stream, n_rows, ids);
   WG_LAUNCH_CHECK();
   if (L->reordered) {
@@ -411,6 +447,30 @@ int build_operator(wg_laplacian_s* L, const int64_t* indptr, const int32_t* indi
                                                           stream);
     });
     if (rc) return rc;
+    // ties (same length, same closed-form status) by hottest, then second-hottest neighbour, then
+    // caller order -- where rows and columns share one numbering (no shard, no literal operator)
+    if (!L->caller_ties && !raw && w_cols == nullptr && n_rows == n_cols && nnz > 0) {
+      unsigned long long* tie;
+      int32_t* ids2;
+      if ((rc = tmp.alloc(&tie, n_rows)) || (rc = tmp.alloc(&ids2, n_rows))) return rc;
+      hipLaunchKernelGGL(invert_perm_kernel, dim3(nb_rows), dim3(256), 0, stream, n_rows, L->perm, L->iperm);
+      WG_LAUNCH_CHECK();
+      hipLaunchKernelGGL(tie_key_kernel, dim3(ceil_div(n_rows, 4)), dim3(kBlock), 0, stream, n_rows, indptr, indices,
+                         L->iperm, tie);
+      WG_LAUNCH_CHECK();
+      // stable passes, least significant key first: (tie, caller index), then the degree key
+      rc = cub_call(stream, [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, tie, key_sorted, ids, ids2, (int)n_rows, 0, 64, stream);
+      });
+      if (rc) return rc;
+      hipLaunchKernelGGL(gather_key_kernel, dim3(nb_rows), dim3(256), 0, stream, n_rows, ids2, key, tie);
+      WG_LAUNCH_CHECK();
+      rc = cub_call(stream, [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairsDescending(t, b, tie, key_sorted, ids2, L->perm, (int)n_rows, 0, 33,
+                                                            stream);
+      });
+      if (rc) return rc;
+    }
     WG_HIP_TRY(hipMemsetAsync(npure_d, 0, sizeof(unsigned int), stream));
     hipLaunchKernelGGL(count_pure_kernel, dim3(nb_rows), dim3(256), 0, stream, n_rows, key, npure_d);
     WG_LAUNCH_CHECK();
@@ -595,6 +655,7 @@ int wg_laplacian_create(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64
   L->nnz_input = nnz;
   L->reordered = !(flags & WG_FLAG_NO_REORDER);
   L->values_null = (values == nullptr);
+  L->caller_ties = (flags & WG_FLAG_CALLER_TIES) != 0;
   int rc = build_operator(L, indptr, indices, values, w_cols, /*raw=*/false, as_stream(stream_));
   if (rc == WG_OK && !(flags & WG_FLAG_KEEP_COLUMN_ORDER)) rc = sort_row_columns(L, as_stream(stream_));
   if (rc != WG_OK) {

@@ -17,6 +17,7 @@ WG_FLAG_NONE = 0
 WG_FLAG_NO_REORDER = 1
 WG_FLAG_TRANSPOSE = 2
 WG_FLAG_KEEP_COLUMN_ORDER = 4
+WG_FLAG_CALLER_TIES = 8
 
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32

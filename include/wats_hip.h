@@ -47,6 +47,10 @@ enum wg_status {
 #define WG_FLAG_KEEP_COLUMN_ORDER 4u /* keep each row's input entry order (default: ascending
                                         internal column, which shares cache lines between
                                         neighbouring gathers on power-law graphs) */
+#define WG_FLAG_CALLER_TIES 8u  /* wg_laplacian_create: rows of equal length keep the caller's
+                                   order (default on a whole graph: by their hottest and
+                                   second-hottest neighbour, then caller order, so rows that
+                                   gather the same hub rows share waves and cache lines) */
 
 typedef struct wg_laplacian_s* wg_laplacian_t;
 
