@@ -78,14 +78,18 @@ class WATS(torch.nn.Module):
         t = self.net(self.wavelet_feats.to(self.device)).squeeze()
         return torch.log(torch.exp(t) + torch.tensor(1.1, device=self.device)).to(self.device)
 
-    def forward(self, x, adj):
-        """WATS.py:112-130."""
-        x, adj = x.to(self.device), adj.to(self.device)
+    def forward(self, x, adj, **base_kwargs):
+        """WATS.py:112-130.  Extra keyword arguments go to ``base_model`` (e.g.
+        ``probe=`` of ``SparseCompatibleGCN``, the edge gradients of the calibrated model), and an
+        ``adj`` that is not a tensor (that model's ``RowNormalizedAdjacency``) is handed on as it is."""
+        x = x.to(self.device)
+        if torch.is_tensor(adj):
+            adj = adj.to(self.device)
         if self.fused_head:
             from .head import wats_head
-            return wats_head(self.wavelet_feats, self.base_model(x, adj), self.net)
+            return wats_head(self.wavelet_feats, self.base_model(x, adj, **base_kwargs), self.net)
         temperatures = self.temperatures()
-        logits = self.base_model(x, adj)
+        logits = self.base_model(x, adj, **base_kwargs)
         calibrated_logits = logits / temperatures.unsqueeze(1)
         return F.log_softmax(calibrated_logits, dim=1)
 

@@ -10,7 +10,9 @@ Public surface (reference names):
     (applies its operator literally), graph_wavelet_features,
     WATS  (calibrator), NormalizedLaplacian (device L_hat handle).
 Section 8(f): SparseCompatibleGCN / RowNormalizedAdjacency (the base model's
-propagation as a HIP SpMM), metrics (device ECE).
+propagation as a HIP SpMM), EdgeProbe / target_flip_scores / toggle_edges
+(its gradient at edge positions and the attack's flip, HIP SDDMM), metrics
+(device ECE).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -26,7 +28,17 @@ from .wavelet import (  # noqa: F401
     row_l1_normalize,
 )
 from .WATS import WATS, accuracy  # noqa: F401
-from .gcn import RowNormalizedAdjacency, SparseCompatibleGCN, propagate  # noqa: F401
+from .gcn import (  # noqa: F401
+    EdgeProbe,
+    RowNormalizedAdjacency,
+    SparseCompatibleGCN,
+    propagate,
+    rowdot,
+    sddmm,
+    target_flip_scores,
+    target_scores_from_grad,
+    toggle_edges,
+)
 from .head import wats_head  # noqa: F401
 
 __version__ = "0.1.0"

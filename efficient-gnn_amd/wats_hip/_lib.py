@@ -77,6 +77,8 @@ SIGNATURES = {
     "wg_clenshaw_step": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f64, c_f64, c_i32, c_vp]),
     "wg_rownorm_create": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_u32, c_vp, ctypes.POINTER(c_vp)]),
     "wg_spmm": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wg_sddmm": (ctypes.c_int, [c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wg_rowdot": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wg_wats_head_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 8 + [c_vp]),
     "wg_wats_head_workspace": (ctypes.c_int, [c_i64, c_i64, c_i32, ctypes.POINTER(c_i64)]),
     "wg_wats_head_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 15 + [c_vp]),

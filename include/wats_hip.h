@@ -380,6 +380,31 @@ int wg_rownorm_create(int64_t n, int64_t nnz, const int64_t* indptr, const int32
 int wg_spmm(wg_laplacian_t op, int64_t F, const float* x, float* y, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Edge-position gradients of that propagation.  The reference attacks take
+ * grad = d loss / d adj through the dense CompatibleGCN.forward (reference
+ * src/gnn/model.py:43-52) and read row t and column t of it
+ * (calib_attack/calib_fga.py:864-881).  For y = adj_norm(A) @ x with upstream
+ * gradient g = d loss / d y and deg as above (0 -> 1),
+ *     d loss / d a_ij = ( g_i . x_j  -  g_i . y_i ) / deg_i
+ * at every (i, j), stored or not: a sampled dense-dense product at a list of
+ * positions plus a per-row term,
+ *     wg_sddmm(rows, cols, g, x, row_term = wg_rowdot(g, y), row_scale = 1 / deg).
+ * wg_sddmm:
+ *   out[p] = row_scale[r] * ( sum_f A[r,f]*B[c,f]  -  row_term[r] ),  r = rows[p], c = cols[p]
+ *   row_term / row_scale nullable (0 / 1).  A is (n_a, F), B is (n_b, F), row-major, stride F;
+ *   0 <= rows[p] < n_a, 0 <= cols[p] < n_b (checked on the device in the bounds-checked variant only).
+ * wg_rowdot:
+ *   out[i] = sum_f A[i,f]*B[i,f]   (the row term g_i . y_i)
+ * Products and sums in float64 in a fixed order, no atomics: bitwise
+ * reproducible.  Asynchronous, no allocation, may be captured.  n_pairs == 0
+ * (n == 0) is WG_OK with no launch.
+ * ---------------------------------------------------------------------- */
+int wg_sddmm(int64_t n_pairs, const int32_t* rows, const int32_t* cols, int64_t F,
+             const float* A, int64_t n_a, const float* B, int64_t n_b,
+             const float* row_term, const float* row_scale, float* out, void* stream);
+int wg_rowdot(int64_t n, int64_t F, const float* A, const float* B, float* out, void* stream);
+
+/* -------------------------------------------------------------------------
  * Section 8(f)-3: the WATS temperature head, fused.  Reference
  * calibration/WATS.py:101-105 (net = Linear(F,16) - ReLU - Linear(16,1)) and
  * :124-130 (T = log(exp(net(H)) + 1.1); out = log_softmax(logits / T)).
