@@ -585,13 +585,6 @@ const void* solo_kernel(int E) {
   }
 }
 
-template <typename T>
-int upload(T** d, const std::vector<T>& h) {
-  if (int rc = dmalloc(d, h.size())) return rc;
-  if (!h.empty()) WG_HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-  return WG_OK;
-}
-
 // rows r0..r1 (descending length) as wave passes: runs of rows sharing a team size TS (~4
 // entries per lane, at most 64 lanes), 64 / TS rows per pass
 void make_passes(const std::vector<int32_t>& rp, int64_t r0, int64_t r1, std::vector<int2>& out,
@@ -782,11 +775,9 @@ int build_solo_plan(wg_laplacian_s* L, ChainPlan* p, const std::vector<int32_t>&
 
 int build_chain_plan(wg_laplacian_s* L, ChainPlan* p) {
   const int64_t na = L->n_active;
-  std::vector<int32_t> rp(na + 1);
-  WG_HIP_TRY(hipMemcpy(rp.data(), L->rowptr, sizeof(int32_t) * (na + 1), hipMemcpyDeviceToHost));
+  std::vector<int32_t> rp, col;
+  if (int rc = download_csr(L, na, L->col, nullptr, &rp, &col)) return rc;
   const int64_t nnz = rp[na];
-  std::vector<int32_t> col(std::max<int64_t>(nnz, 1));
-  if (nnz) WG_HIP_TRY(hipMemcpy(col.data(), L->col, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
   std::vector<uint16_t> ids(std::max<int64_t>(nnz, 1));
   for (int64_t e = 0; e < nnz; ++e) {
     if (col[e] < 0 || col[e] >= na) return fail(WG_ERR_INVALID, "chain plan: column %d outside the active rows", col[e]);

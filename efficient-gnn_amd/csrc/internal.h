@@ -9,11 +9,10 @@
 #include <string>
 #include <vector>
 
+#include "plan_host.h"
 #include "wats_hip.h"
 
 namespace wg {
-
-int fail(int code, const char* fmt, ...);
 
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes) once per (kernel, current device):
 // the attribute is per device, so a process-wide "done" flag would skip it on a second device
@@ -50,11 +49,8 @@ int n_cus(int dev);
 #endif
 
 constexpr int kBlock = 256;   // 4 waves of 64 lanes
-constexpr int kMaxSeg = 24;
-constexpr int kBuckets = 33;  // row-length buckets: b=0: len<=1; b>0: 2^(b-1) < len <= 2^b
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 template <typename T>
 int dmalloc(T** p, size_t count) {
@@ -64,28 +60,24 @@ int dmalloc(T** p, size_t count) {
   return WG_OK;
 }
 
-// ---------------------------------------------------------------------------
-// Step-kernel launch plan (per signal-tile shape), see step.hip.
-// ---------------------------------------------------------------------------
-struct Seg {
-  int32_t begin;      // team mode: internal rows [begin, end); chunk mode: chunk ids
-  int32_t end;
-  int32_t blk_begin;  // first workgroup of this segment
-  int32_t ln;         // team mode: lane sub-groups cooperating on one row
-  int32_t mode;       // 0 = team, 1 = block (workgroup per row), 2 = split (workgroup per nnz chunk)
-};
+// a host table on the device (*d stays null on failure: non-null pointers mark a built table)
+template <typename T>
+int upload(T** d, const std::vector<T>& h) {
+  if (int rc = dmalloc(d, h.size())) return rc;
+  if (!h.empty() && hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(*d);
+    *d = nullptr;
+    return fail(WG_ERR_HIP, "upload of %zu bytes failed", sizeof(T) * h.size());
+  }
+  return WG_OK;
+}
 
-struct SegTable {
-  Seg s[kMaxSeg];
-  int32_t n;
-  int32_t total_blocks;
-};
-
-struct ChunkDesc {  // one workgroup's share of a split row
-  int32_t row;
-  int32_t e0, e1;   // nnz range
-  int32_t pad;
-};
+// hipFree every pointer and null it
+template <typename... P>
+void free_all(P*&... p) {
+  ((void)hipFree(p), ...);
+  ((p = nullptr), ...);
+}
 
 // the wave table of the value-free VEC-4 step as independent waves (team.hip)
 struct TeamPlan {
@@ -207,7 +199,7 @@ struct TilePlan {
 };
 
 struct Tuning {
-  // 0 = shape-dependent default (see default_knobs in step.hip)
+  // 0 = shape-dependent default (see default_knobs in plan_host.cpp)
   int32_t iter = 0;          // team mode: target nonzeros per lane sub-group
   int32_t block_iter = 0;    // block mode: rows up to NW*G*block_iter nonzeros get one workgroup
   int32_t chunk_iter = 0;    // split mode: NW*G*chunk_iter nonzeros per workgroup chunk
@@ -410,6 +402,26 @@ struct wg_laplacian_s {
 };
 
 namespace wg {
+// Rows [0, n) of L's CSR on the host for a planner (plan_host.h): the row starts rs [n + 1]; col (if
+// wanted): their rs[n] column ids from dcol (the operator's L->col, or the hybrid step's tail-first
+// copy); re (if wanted): the row ends, from drsplit (the hybrid tails' ends) or rs + 1
+inline int download_csr(const wg_laplacian_s* L, int64_t n, const int32_t* dcol, const int32_t* drsplit,
+                        std::vector<int32_t>* rs, std::vector<int32_t>* col, std::vector<int32_t>* re = nullptr) {
+  if (n < 0 || n > L->n_rows)
+    return fail(WG_ERR_INVALID, "download_csr: %lld of %lld rows", (long long)n, (long long)L->n_rows);
+  rs->resize(n + 1);
+  WG_HIP_TRY(hipMemcpy(rs->data(), L->rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
+  if (col) {
+    col->resize((*rs)[n]);
+    if ((*rs)[n]) WG_HIP_TRY(hipMemcpy(col->data(), dcol, sizeof(int32_t) * (*rs)[n], hipMemcpyDeviceToHost));
+  }
+  if (re) {
+    re->assign(rs->begin() + 1, rs->end());
+    if (drsplit && n) WG_HIP_TRY(hipMemcpy(re->data(), drsplit, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  }
+  return WG_OK;
+}
+
 // prologue.hip
 int build_operator(wg_laplacian_s* L, const int64_t* indptr, const int32_t* indices, const float* values,
                    const float* w_cols, bool raw, hipStream_t stream);

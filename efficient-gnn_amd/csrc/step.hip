@@ -503,13 +503,6 @@ __global__ __launch_bounds__(kBlock) void hybrid_epilogue_kernel(StepArgs a, int
   step_epilogue<4>(a, row, fs, acc, in, sg * LF);
 }
 
-// smallest divisor of G that is >= want (G itself if none smaller)
-int divisor_at_least(int G, int64_t want) {
-  for (int d = 1; d <= G; ++d)
-    if (G % d == 0 && d >= want) return d;
-  return G;
-}
-
 template <int VEC, int NW>
 void launch_main(const Plan& plan, const StepArgs& a, hipStream_t stream) {
   const dim3 grid(plan.tab.total_blocks), block(NW * 64);
@@ -571,31 +564,9 @@ int launch_step_vec(const Plan& plan, const StepArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-namespace {
-int upload_segs(Plan& p) {
-  int rc = dmalloc(&p.d_segs, kMaxSeg);
-  if (rc) return rc;
-  WG_HIP_TRY(hipMemcpy(p.d_segs, p.tab.s, sizeof(Seg) * kMaxSeg, hipMemcpyHostToDevice));
-  return WG_OK;
-}
-}  // namespace
-
 void Plan::release() {
   team.release();
-  (void)hipFree(wmeta);
-  (void)hipFree(sell);
-  wmeta = nullptr;
-  sell = nullptr;
-  (void)hipFree(d_segs);
-  d_segs = nullptr;
-  (void)hipFree(chunks);
-  (void)hipFree(partial);
-  (void)hipFree(rowchunks);
-  (void)hipFree(arrivals);
-  arrivals = nullptr;
-  chunks = nullptr;
-  partial = nullptr;
-  rowchunks = nullptr;
+  free_all(wmeta, sell, d_segs, chunks, partial, rowchunks, arrivals);
 }
 
 int pick_vec(int64_t F, std::initializer_list<const void*> ptrs) {
@@ -609,54 +580,7 @@ int pick_vec(int64_t F, std::initializer_list<const void*> ptrs) {
   return 1;
 }
 
-// Defaults measured on MI355X (profiles/r01 sweeps): wide signals (G = 64/LF
-// small, e.g. F = 40 -> G = 6) want long per-sub-group runs; F = 1 (G = 64)
-// shorter ones.
-// Wide tiles (F >= 16) on large graphs: one sub-group per row up to 192 entries per
-// lane (ogbn-arxiv-size F=40: 41.8 vs 45.5 us per step with iter 96 vs 24; F=64 56.3
-// vs 64.9; Reddit-size F=44 1732 vs 1817 us; with the value-free Clenshaw chain,
-// s47-s49: 192 vs 96 -- arxiv F=40 37.3 vs 38.2, F=64 49.9 vs 51.8, Reddit-size F=44
-// 1497 vs 1522; 256 jumps to 55 us) and long split-row chunks (Reddit-size
-// F=44: 1625 us with chunk_iter 128 vs 1729 with 64) above 16 M nonzeros, 64 below
-// (arxiv F=40 36.5 vs 37.1 us, F=64 neutral; profiles/r01/s55_chunk_sweep.log); small graphs
-// keep more lanes per row for latency (PubMed-size F=40: 9.3 us with iter 24, 17.2
-// with 96).  F = 1 from 1 M nonzeros: 8 entries per lane (ogbn-arxiv-size: 10.7 us per
-// step vs 11.6 with 16, s34).
-void default_knobs(const Tuning& t, int G, int64_t nnz, int* iter, int* block_iter, int* chunk_iter,
-                   bool hybrid = false, int64_t rows = 0) {
-  // the hybrid step's tail (~22 % of each row's entries) wants longer one-row
-  // sub-groups and larger block / split units the more rows there are to fill the CUs with
-  // (Reddit-size F=41, rows / (G x 256 CUs): 182 -> iter 6144: 784 vs 917 us per step with the
-  // gather kernel's defaults; its 2-way shards (92) -> 1536: 415 vs 473; the 4-way shards (46)
-  // keep the defaults: 1536 gives 232-234 vs 246-249 on three ranks but 312 vs 247 on the fourth
-  // (a long-tailed row walked by one sub-group), the 8-way shards (23) 172 vs 156;
-  // profiles/r02/s72-s76).  Only from 8 M nonzeros: on the arxiv-size graph (2.3 M, hub rows of
-  // thousands of tail entries walked by one sub-group) the 1536 tier took 67.8 vs 38.6 us
-  // (profiles/r03/s20-s21)
-  const int64_t per_cu = rows / ((int64_t)G * 256);
-  if (hybrid && per_cu >= 64 && nnz >= ((int64_t)8 << 20)) {
-    const bool big = per_cu >= 128;
-    *iter = t.iter > 0 ? t.iter : (big ? 6144 : 1536);
-    *block_iter = t.block_iter > 0 ? t.block_iter : (big ? 4096 : 1024);
-    *chunk_iter = t.chunk_iter > 0 ? t.chunk_iter : (big ? 4096 : 1024);
-    return;
-  }
-  const bool wide = G <= 16;
-  const bool big = nnz >= (int64_t)1 << 20;
-  // from 8 M nonzeros: longer team runs and 256-iteration split-row chunks (Reddit-size F=41,
-  // width 48: 1400 vs 1434 us per step; its 8-way shard, 14.3 M nonzeros: 195-200 vs 207-211
-  // with the 1-16 M defaults, profiles/r02/s39-s40)
-  const bool large = nnz >= (int64_t)1 << 23;
-  *iter = t.iter > 0 ? t.iter : (wide ? (large ? 384 : big ? 192 : 24) : (G == 64 && big ? 8 : 16));
-  *block_iter = t.block_iter > 0 ? t.block_iter : (wide ? 256 : 32);
-  *chunk_iter = t.chunk_iter > 0 ? t.chunk_iter : (wide ? (large ? 256 : big ? 64 : 32) : 16);
-}
-
-// Build (once per tile shape) the segment table and the split-row chunk table.
-//   team  rows: len <= G*iter              (LN sub-groups per row, LN | G)
-//   block rows: len <= 4G*block_iter       (one workgroup per row)
-//   split rows: longer                     (one workgroup per CH = 4G*chunk_iter nnz + combine_kernel)
-// Classification is by power-of-two length bucket (rows are sorted by length).
+// Build (once per tile shape) the segment table and the split-row chunk table (plan_segments).
 int get_plan(wg_laplacian_s* L, int LF, int VEC, bool active_only, Plan** out, bool hybrid) {
   active_only = active_only && L->reordered;
   const int NW = (L->tune.waves == 16 || L->tune.waves == 8) ? L->tune.waves : 4;
@@ -672,114 +596,39 @@ int get_plan(wg_laplacian_s* L, int LF, int VEC, bool active_only, Plan** out, b
   p.nw = NW;
   if (LF == 1 && VEC == 1 && L->tune.hot > 0)
     p.hot = (int32_t)std::min<int64_t>({(int64_t)L->tune.hot, L->n_cols, (int64_t)((160 * 1024 - NW * 64 * 8) / 4)});
-  const int G = 64 / LF;
   const int64_t n = active_only ? L->n_active : L->n_rows;
   unsigned int bucket[kBuckets];
-  const int64_t base = 0;  // first row of the plan
   for (int b = 0; b < kBuckets; ++b) bucket[b] = L->bucket[b];
   bucket[0] -= (unsigned int)(L->n_rows - n);  // closed-form rows: length 0, at the very end
-  p.row0 = base;
+  p.row0 = 0;
   p.row1 = n;
-  int iter, block_iter, chunk_iter;
-  default_knobs(L->tune, G, L->nnz, &iter, &block_iter, &chunk_iter, hybrid, n);
-  const int64_t team_max = (int64_t)G * iter;
-  const int64_t block_max = (int64_t)NW * G * block_iter;
-  const int64_t CH = (int64_t)NW * G * chunk_iter;
-  SegTable& t = p.tab;
-  char buf[256];
-  if (!L->reordered) {
-    // caller order: a single team segment sized by the average row length
-    const int ln = divisor_at_least(G, ceil_div(std::max<int64_t>(1, L->avg_len), iter));
-    const int tpw = G / ln;
-    t.s[0] = Seg{0, (int32_t)n, 0, ln, 0};
-    t.n = n > 0 ? 1 : 0;
-    t.total_blocks = (int32_t)ceil_div(n, NW * tpw);
-    snprintf(buf, sizeof(buf), "team rows[0,%lld) ln=%d (no reorder)\n", (long long)n, ln);
-    p.text = buf;
-    if (int rc2 = upload_segs(p)) return rc2;
-    auto res = L->plans.emplace(key, p);
-    *out = &res.first->second;
-    return WG_OK;
+  SegKnobs kn;
+  kn.G = 64 / LF;
+  kn.NW = NW;
+  kn.reordered = L->reordered;
+  kn.avg_len = L->avg_len;
+  default_knobs(L->tune.iter, L->tune.block_iter, L->tune.chunk_iter, kn.G, L->nnz, &kn.iter, &kn.block_iter,
+                &kn.chunk_iter, hybrid, n);
+  std::vector<int32_t> rp;  // the split rows' row starts
+  if (const int64_t n_split = count_split_rows(kn, bucket))
+    if (int rc = download_csr(L, n_split, nullptr, nullptr, &rp, nullptr)) return rc;
+  SegPlan sp;
+  if (int rc = plan_segments(kn, n, bucket, rp, &sp)) return rc;
+  p.tab = sp.tab;
+  p.n_split = sp.n_split;
+  p.n_chunks = (int32_t)sp.chunks.size();
+  p.text = std::move(sp.text);
+  int rc = upload(&p.d_segs, std::vector<Seg>(p.tab.s, p.tab.s + kMaxSeg));
+  if (!rc && p.n_split > 0) {
+    rc = upload(&p.chunks, sp.chunks);
+    if (!rc) rc = upload(&p.rowchunks, sp.rowchunks);
+    if (!rc) rc = dmalloc(&p.partial, sp.chunks.size() * (size_t)p.width);
+    if (!rc) rc = dmalloc(&p.arrivals, sp.rowchunks.size());
+    if (!rc && hipMemset(p.arrivals, 0, sizeof(uint32_t) * sp.rowchunks.size()) != hipSuccess) rc = WG_ERR_HIP;
   }
-  int64_t n_split = 0, n_block = 0;
-  for (int b = kBuckets - 1; b >= 0; --b) {
-    const int64_t maxlen = (b == 0) ? 1 : (1ll << b);
-    if (maxlen > block_max) n_split += bucket[b];
-    else if (maxlen > team_max) n_block += bucket[b];
-  }
-  int nseg = 0;
-  int32_t blk = 0;
-  if (n_split > 0) {
-    std::vector<int32_t> rp(n_split + 1);
-    WG_HIP_TRY(hipMemcpy(rp.data(), L->rowptr + base, sizeof(int32_t) * (n_split + 1), hipMemcpyDeviceToHost));
-    std::vector<ChunkDesc> ch;
-    std::vector<int2> rc(n_split);
-    for (int64_t r = 0; r < n_split; ++r) {
-      const int64_t len = rp[r + 1] - rp[r];
-      const int cnt = (int)std::max<int64_t>(1, ceil_div(len, CH));
-      rc[r] = make_int2((int)ch.size(), cnt);
-      for (int q = 0; q < cnt; ++q) {
-        ChunkDesc d{};
-        d.row = (int32_t)(base + r);
-        d.e0 = (int32_t)(rp[r] + q * CH);
-        d.e1 = (int32_t)std::min<int64_t>(rp[r + 1], rp[r] + (q + 1) * CH);
-        ch.push_back(d);
-      }
-    }
-    p.n_chunks = (int32_t)ch.size();
-    p.n_split = (int32_t)n_split;
-    int rc_ = dmalloc(&p.chunks, ch.size());
-    if (!rc_) rc_ = dmalloc(&p.partial, ch.size() * (size_t)p.width);
-    if (!rc_) rc_ = dmalloc(&p.rowchunks, rc.size());
-    if (!rc_) rc_ = dmalloc(&p.arrivals, rc.size());
-    if (!rc_ && hipMemset(p.arrivals, 0, sizeof(uint32_t) * rc.size()) != hipSuccess) rc_ = WG_ERR_HIP;
-    if (rc_) {
-      p.release();
-      return rc_;
-    }
-    WG_HIP_TRY(hipMemcpy(p.chunks, ch.data(), sizeof(ChunkDesc) * ch.size(), hipMemcpyHostToDevice));
-    WG_HIP_TRY(hipMemcpy(p.rowchunks, rc.data(), sizeof(int2) * rc.size(), hipMemcpyHostToDevice));
-    t.s[nseg++] = Seg{0, p.n_chunks, 0, G, 2};
-    blk = p.n_chunks;
-    snprintf(buf, sizeof(buf), "split rows[%lld,%lld) chunks=%d CH=%lld (+combine)\n", (long long)base,
-             (long long)(base + n_split), p.n_chunks, (long long)CH);
-    p.text += buf;
-  }
-  if (n_block > 0) {
-    t.s[nseg++] = Seg{(int32_t)(base + n_split), (int32_t)(base + n_split + n_block), blk, G, 1};
-    blk += (int32_t)n_block;
-    snprintf(buf, sizeof(buf), "block rows[%lld,%lld) (workgroup per row)\n", (long long)(base + n_split),
-             (long long)(base + n_split + n_block));
-    p.text += buf;
-  }
-  int32_t row = (int32_t)(base + n_split + n_block);
-  const int first_team = nseg;
-  for (int b = kBuckets - 1; b >= 0; --b) {
-    const int32_t cnt = (int32_t)bucket[b];
-    const int64_t maxlen = (b == 0) ? 1 : (1ll << b);
-    if (!cnt || maxlen > team_max) continue;
-    int ln = divisor_at_least(G, ceil_div(maxlen, iter));
-    Seg* last = nseg > first_team ? &t.s[nseg - 1] : nullptr;
-    if (last && (last->ln == ln || nseg == kMaxSeg)) {
-      if (last->ln != ln) ln = last->ln;  // out of slots: extend
-      last->end = row + cnt;
-      blk = last->blk_begin + (int32_t)ceil_div(last->end - last->begin, NW * (G / ln));
-    } else {
-      t.s[nseg++] = Seg{row, row + cnt, blk, ln, 0};
-      blk += (int32_t)ceil_div(cnt, NW * (G / ln));
-    }
-    row += cnt;
-  }
-  t.n = nseg;
-  t.total_blocks = blk;
-  for (int i = first_team; i < nseg; ++i) {
-    snprintf(buf, sizeof(buf), "team rows[%d,%d) ln=%d blocks=%d\n", t.s[i].begin, t.s[i].end, t.s[i].ln,
-             (i + 1 < nseg ? t.s[i + 1].blk_begin : blk) - t.s[i].blk_begin);
-    p.text += buf;
-  }
-  if (int rc2 = upload_segs(p)) {
+  if (rc) {
     p.release();
-    return rc2;
+    return rc;
   }
   auto res = L->plans.emplace(key, p);
   *out = &res.first->second;
@@ -816,103 +665,27 @@ bool gather4_applies(const wg_laplacian_s* L, int64_t F) {
 
 int build_pcol(wg_laplacian_s* L) {
   if (L->pcol) return WG_OK;
-  const int64_t n = L->n_rows;
-  std::vector<int32_t> rp(n + 1);
-  WG_HIP_TRY(hipMemcpy(rp.data(), L->rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
-  std::vector<int32_t> col(std::max<int64_t>(rp[n], 1));
-  if (rp[n]) WG_HIP_TRY(hipMemcpy(col.data(), L->col, sizeof(int32_t) * rp[n], hipMemcpyDeviceToHost));
-  std::vector<int32_t> prp(n + 1);
-  prp[0] = 0;
-  for (int64_t r = 0; r < n; ++r) {
-    const int64_t len = rp[r + 1] - rp[r];
-    const int64_t padded = prp[r] + (len + 3) / 4 * 4;
-    if (padded > INT32_MAX - kPcolTail) return fail(WG_ERR_INVALID, "build_pcol: padded CSR exceeds int32");
-    prp[r + 1] = (int32_t)padded;
-  }
-  std::vector<int32_t> pc((size_t)prp[n] + kPcolTail, kPadCol);
-  for (int64_t r = 0; r < n; ++r)
-    std::copy(col.begin() + rp[r], col.begin() + rp[r + 1], pc.begin() + prp[r]);
-  int32_t *dprp = nullptr, *dpc = nullptr;
-  if (int rc = dmalloc(&dprp, prp.size())) return rc;
-  if (int rc = dmalloc(&dpc, pc.size())) {
-    (void)hipFree(dprp);
-    return rc;
-  }
-  WG_HIP_TRY(hipMemcpy(dprp, prp.data(), sizeof(int32_t) * prp.size(), hipMemcpyHostToDevice));
-  WG_HIP_TRY(hipMemcpy(dpc, pc.data(), sizeof(int32_t) * pc.size(), hipMemcpyHostToDevice));
-  L->prp = dprp;
-  L->pcol = dpc;
-  return WG_OK;
+  std::vector<int32_t> rp, col;
+  if (int rc = download_csr(L, L->n_rows, L->col, nullptr, &rp, &col)) return rc;
+  PaddedCsr pc;
+  int rc = plan_pcol(rp, col, &pc);
+  if (!rc) rc = upload(&L->prp, pc.prp);
+  if (!rc) rc = upload(&L->pcol, pc.pcol);
+  if (rc) free_all(L->prp, L->pcol);
+  return rc;
 }
 
-// The SELL order of a plan's value-free team waves (accumulate_sell): for wave w = unit * NW + wave
-// of a team segment, sub-group g (row begin + (unit - blk_begin) NW tpw + wave tpw + g / LN, share
-// ns = g % LN of the row's 4-entry chunks: ns, ns + LN, ...), its k-th chunk at
-// sell[wmeta[w].x + k G + g] with k = 2 t + c; every sub-group padded with kPadCol chunks to the
-// wave's turn count wmeta[w].y (2 chunks per turn), plus 2 turns of pads after the last wave.
+// The SELL order of a plan's value-free team waves (plan_sell; accumulate_sell reads it)
 int build_sell(wg_laplacian_s* L, Plan* p, int LF) {
   if (p->sell) return WG_OK;
-  const int G = 64 / LF;
-  const int NW = p->nw;
-  const int64_t n = L->n_rows;
-  std::vector<int32_t> rp(n + 1);
-  WG_HIP_TRY(hipMemcpy(rp.data(), L->rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
-  std::vector<int32_t> col(std::max<int64_t>(rp[n], 1));
-  if (rp[n]) WG_HIP_TRY(hipMemcpy(col.data(), L->col, sizeof(int32_t) * rp[n], hipMemcpyDeviceToHost));
-  std::vector<int2> wm((size_t)p->tab.total_blocks * NW, int2{0, 0});
-  std::vector<int4> sell;
-  const int4 pad4{kPadCol, kPadCol, kPadCol, kPadCol};
-  for (int si = 0; si < p->tab.n; ++si) {
-    const Seg& sg = p->tab.s[si];
-    if (sg.mode != 0) continue;
-    const int LN = sg.ln, tpw = G / LN;
-    const int32_t nblk = (si + 1 < p->tab.n ? p->tab.s[si + 1].blk_begin : p->tab.total_blocks) - sg.blk_begin;
-    for (int32_t u = 0; u < nblk; ++u) {
-      for (int w = 0; w < NW; ++w) {
-        const int64_t r0 = (int64_t)sg.begin + (int64_t)u * NW * tpw + (int64_t)w * tpw;
-        int64_t turns = 0;
-        for (int g = 0; g < G; ++g) {  // the wave's longest sub-group
-          const int64_t r = r0 + g / LN, ns = g % LN;
-          if (g / LN >= tpw || r >= sg.end) continue;
-          const int64_t nch = (rp[r + 1] - rp[r] + 3) / 4;
-          const int64_t mine = ns < nch ? (nch - ns + LN - 1) / LN : 0;
-          turns = std::max<int64_t>(turns, (mine + 1) / 2);
-        }
-        const size_t wi = (size_t)(sg.blk_begin + u) * NW + w;
-        if (sell.size() + (size_t)(2 * G * (turns + 2)) >= ((size_t)1 << 27))  // 16-B chunks at 32-bit byte offsets
-          return fail(WG_ERR_UNSUPPORTED, "build_sell: id array exceeds 2 GB (tuning key sell = 0)");
-        wm[wi] = int2{(int)sell.size(), (int)(2 * turns)};  // chunk count (accumulate_sell)
-        const size_t base = sell.size();
-        sell.resize(base + (size_t)2 * turns * G, pad4);
-        for (int g = 0; g < G; ++g) {
-          const int64_t r = r0 + g / LN, ns = g % LN;
-          if (g / LN >= tpw || r >= sg.end) continue;
-          const int64_t len = rp[r + 1] - rp[r];
-          const int64_t nch = (len + 3) / 4;
-          for (int64_t k = 0; ns + k * LN < nch; ++k) {
-            const int64_t ch = ns + k * LN;
-            int32_t id[4];
-            for (int i = 0; i < 4; ++i) id[i] = ch * 4 + i < len ? col[rp[r] + ch * 4 + i] : kPadCol;
-            sell[base + (size_t)k * G + g] = int4{id[0], id[1], id[2], id[3]};
-          }
-        }
-      }
-    }
-  }
-  sell.resize(sell.size() + (size_t)4 * G, pad4);  // the next-turn id reads past the last wave
-  auto undo = [&](int rc) {  // no half-built table: the next call builds both arrays again
-    (void)hipFree(p->wmeta);
-    (void)hipFree(p->sell);
-    p->wmeta = nullptr;
-    p->sell = nullptr;
-    return rc;
-  };
-  if (int rc = dmalloc(&p->wmeta, wm.size())) return undo(rc);
-  if (int rc = dmalloc(&p->sell, sell.size())) return undo(rc);
-  if (hipMemcpy(p->wmeta, wm.data(), sizeof(int2) * wm.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(p->sell, sell.data(), sizeof(int4) * sell.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return undo(fail(WG_ERR_HIP, "build_sell: upload failed"));
-  return WG_OK;
+  std::vector<int32_t> rp, col;
+  if (int rc = download_csr(L, L->n_rows, L->col, nullptr, &rp, &col)) return rc;
+  SellTable st;
+  int rc = plan_sell(p->tab, p->nw, LF, rp, col, &st);
+  if (!rc) rc = upload(&p->wmeta, st.wmeta);
+  if (!rc) rc = upload(&p->sell, st.sell);
+  if (rc) free_all(p->wmeta, p->sell);  // no half-built table: the next call builds both arrays again
+  return rc;
 }
 
 int launch_step(wg_laplacian_s* L, int32_t k, int64_t F, const float* xm1, const float* xm2, float* xk, float* S,

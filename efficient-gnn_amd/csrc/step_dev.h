@@ -81,12 +81,6 @@ struct StepArgs {
 #endif
 };
 
-// a padded-CSR column id whose byte offset (id * row bytes <= 256) lies past every gathered buffer
-constexpr int32_t kPadCol = 0xFFFFFF;
-// kPadCol ids after the last row of pcol: a sub-group's id loads run up to (PF + 1) turns of CPT
-// steps (<= 4096 ids each) past its range
-constexpr int32_t kPcolTail = 65536;
-
 // the entry range of a row (or of a split-row chunk) this launch's phase covers
 __device__ __forceinline__ void phase_range(const StepArgs& a, int64_t row, int32_t& e0, int32_t& e1) {
   if (a.phase == 0) return;

@@ -43,9 +43,6 @@
 namespace wg {
 namespace {
 
-constexpr int kTC = 32;  // columns per tile (the MFMA's K)
-constexpr int kItemMax = 1024;  // dense blocks per work item (tile_max <= 1024)
-
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -135,7 +132,7 @@ __device__ __forceinline__ void tiles_item(const TileArgs& t, int item) {
   const int fb0 = FW ? wave % NFB : 0;             // its first column block
   const int mrow = 16 * RG * rwave + (lane & 15);  // this lane's A row of row group 0 (of the block)
   const int mshift = 8 * (lane >> 4);              // its byte of the 32-bit row mask
-  const int32_t b0 = it.y, n = it.z - it.y;  // n <= kItemMax (build_tile_plan)
+  const int32_t b0 = it.y, n = it.z - it.y;  // n <= kItemMax (plan_tiles)
   WG_DCHECK(b0 >= 0 && n >= 0 && n <= kItemMax && (int64_t)it.z <= t.dbg_blocks && it.w < (int)t.dbg_slots &&
                 rb * TR < t.n_plan,
             "tile item %d: {%d, %d, %d, %d} outside %lld blocks / %lld slots / %lld rows", item, it.x, it.y, it.z, it.w,
@@ -520,183 +517,64 @@ __global__ void scale_rows_kernel(int64_t n, int64_t F, const float* __restrict_
   u[i] = (float)((double)x[i] * dinv[i / F]);
 }
 
-template <typename T>
-int upload(T** d, const std::vector<T>& h) {
-  if (int rc = dmalloc(d, h.size())) return rc;
-  if (!h.empty()) WG_HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-  return WG_OK;
-}
-
+// the plan's tables (plan_tiles) on the device; n_blocks == 0: nothing built, no hybrid step
 int build_tile_plan(wg_laplacian_s* L, bool active_only, TilePlan* p) {
-  const int64_t n = L->n_rows, nnz = L->nnz;
-  const int64_t n_plan = active_only ? L->n_active : n;
+  const int64_t n_plan = active_only ? L->n_active : L->n_rows;
   // closed-form rows are never gathered: on a whole graph they end the column space; on a row shard
   // they sit between the active own rows and the halo (dist.hip keeps their u rows zero)
   const int64_t col_limit = (active_only && L->n_cols == L->n_rows) ? L->n_active : L->n_cols;
-  const int th = std::max(1, L->tune.tile_th);
-  int tmax = L->tune.tile_max;  // <= 0: auto (below)
-  const int kTR = L->tune.tile_rows == 128 ? 128 : 64;
-  p->rows = kTR;
-  std::vector<int32_t> rp(n + 1), col(nnz);
-  WG_HIP_TRY(hipMemcpy(rp.data(), L->rowptr, sizeof(int32_t) * (n + 1), hipMemcpyDeviceToHost));
-  WG_HIP_TRY(hipMemcpy(col.data(), L->col, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost));
-  const int64_t n_ct = ceil_div(L->n_cols, kTC);
-  std::vector<int32_t> cnt(n_ct, 0), sel(n_ct, -1), touched, tmp;
-  std::vector<int32_t> bct, tcol(col), tsplit(n);
-  std::vector<uint32_t> bmask;
-  std::vector<int4> items, multi;
-  std::vector<int2> rbs;  // row blocks with dense blocks: {row block, first block}
-  int32_t n_slots = 0;
-  int64_t dense = 0;
-  for (int64_t r = n_plan; r < n; ++r) tsplit[r] = rp[r + 1];  // unplanned rows: all tail
-  const int64_t n_rb = ceil_div(n_plan, kTR);
-  for (int64_t rb = 0; rb < n_rb; ++rb) {
-    const int64_t r0 = rb * kTR, r1 = std::min<int64_t>(r0 + kTR, n_plan);
-    touched.clear();
-    for (int64_t r = r0; r < r1; ++r)
-      for (int32_t e = rp[r]; e < rp[r + 1]; ++e) {
-        const int32_t c = col[e];
-        if (c < 0 || c >= col_limit) return fail(WG_ERR_INVALID, "tiles: column %d of row %lld outside [0, %lld)", c,
-                                                 (long long)r, (long long)col_limit);
-        if (cnt[c / kTC]++ == 0) touched.push_back(c / kTC);
-      }
-    std::sort(touched.begin(), touched.end());
-    const int32_t first = (int32_t)bct.size();
-    for (int32_t ct : touched)
-      if (cnt[ct] >= th) {
-        sel[ct] = (int32_t)bct.size();
-        bct.push_back(ct);
-      }
-    bmask.resize(bct.size() * kTR, 0u);
-    for (int64_t r = r0; r < r1; ++r) {
-      tmp.clear();
-      for (int32_t e = rp[r]; e < rp[r + 1]; ++e) {
-        const int32_t c = col[e];
-        const int32_t s = sel[c / kTC];
-        if (s >= 0) {
-          uint32_t& w = bmask[(size_t)s * kTR + (r - r0)];
-          const uint32_t bit = 1u << (c % kTC);
-          if (w & bit) {  // a repeated entry: a row mask cannot count it twice -- keep the gather kernel
-            p->n_blocks = 0;
-            return WG_OK;
-          }
-          w |= bit;
-          ++dense;
-        } else {
-          tmp.push_back(c);
-        }
-      }
-      if (L->tune.probe_tailwin > 0) {  // timing probe only (results wrong): every tail column folded
-        const int64_t win = std::max<int64_t>(1, col_limit / L->tune.probe_tailwin);  // into one window
-        for (auto& c : tmp) c = (int32_t)(col_limit / 2 + c % win < col_limit ? col_limit / 2 + c % win : c % win);
-      }
-      tsplit[r] = rp[r] + (int32_t)tmp.size();
-      std::copy(tmp.begin(), tmp.end(), tcol.begin() + rp[r]);
-    }
-    for (int32_t ct : touched) {
-      cnt[ct] = 0;
-      sel[ct] = -1;
-    }
-    const int32_t nb = (int32_t)bct.size() - first;
-    if (nb > 0) rbs.push_back(make_int2((int)rb, first));  // nb == 0: every entry is tail, no part added
+  TileKnobs kn;
+  kn.th = std::max(1, L->tune.tile_th);
+  kn.tile_max = L->tune.tile_max;
+  kn.rows = L->tune.tile_rows == 128 ? 128 : 64;
+  kn.probe_tailwin = L->tune.probe_tailwin;
+  kn.fused_possible = kn.rows == 128 && L->tune.tile_rg == 1 && L->tune.team && L->tune.hyb_conc &&
+                      L->tune.hyb_conc != 3;
+  p->rows = kn.rows;
+  TileTables t;
+  {
+    std::vector<int32_t> rp, col;
+    if (int rc = download_csr(L, L->n_rows, L->col, nullptr, &rp, &col)) return rc;
+    if (int rc = plan_tiles(rp, col, n_plan, L->n_cols, col_limit, kn, &t)) return rc;
   }
-  // work items: a row block's dense blocks, split over several workgroups (slots) past tmax, one list
-  // per form (the plan serves every width; hybrid_fused_shape picks the form per width at launch).  Auto
-  // (tile_max <= 0) for the sequential and two-stream steps: 128 blocks per workgroup from 100 k rows, else 64
-  // (Reddit-size F=41, width 48, us per step: whole graph 726 at 128 vs 735 at 192, 2-way shard 369 vs
-  // 382; smaller shards want more workgroups, profiles/r02/s80-s81).  Where the fused launch takes the
-  // plan (hybrid_fused_kernel: the tail's waves fill the GPU beside the items) fewer, longer items pay,
-  // about n_plan / 310 blocks each: 8-way shard 101.6 at 96 vs 103.9 at 64 and 103.0 at 112, 4-way 173
-  // at 128-192 vs 212.8 at 64 and 196 at 256, 2-way 326-331 at 384 vs 340 at 320 and 368-371 at 512,
-  // whole graph 692-694 at 640-768 vs 705 at 512 and 745 at 1024 (r05 s55-s65)
-  const int64_t nblk = (int64_t)bct.size();
-  // one item list per form: {items, multi, slots}
-  auto make_items = [&](int tm, std::vector<int4>& its, std::vector<int4>& mul) {
-    tm = std::max(1, std::min(tm, kItemMax));
-    int32_t ns = 0;
-    for (size_t q0 = 0; q0 < rbs.size(); ++q0) {
-      const int rb = rbs[q0].x, first = rbs[q0].y;
-      const int32_t nb = (int32_t)((q0 + 1 < rbs.size() ? rbs[q0 + 1].y : nblk) - first);
-      const int32_t k = (nb + tm - 1) / tm;
-      if (k == 1) {
-        its.push_back(make_int4(rb, first, first + nb, -1));
-      } else {
-        for (int32_t q = 0; q < k; ++q)
-          its.push_back(make_int4(rb, first + (int32_t)((int64_t)nb * q / k), first + (int32_t)((int64_t)nb * (q + 1) / k),
-                                  ns + q));
-        mul.push_back(make_int4(rb, ns, k, 0));
-        ns += k;
-      }
-    }
-    return ns;
-  };
-  const int tseq = tmax > 0 ? tmax : (n_plan >= 100000 ? 128 : 64);
-  const int tfus = tmax > 0 ? tmax : (int)std::min<int64_t>(kItemMax, std::max<int64_t>(96, n_plan / 310 / 16 * 16));
-  n_slots = make_items(tseq, items, multi);
-  std::vector<int4> fitems, fmulti;
-  // the fused launch's items only where its tile shape can apply (hybrid_fused_shape decides per width)
-  const bool fused_possible = kTR == 128 && L->tune.tile_rg == 1 && L->tune.team && L->tune.hyb_conc &&
-                              L->tune.hyb_conc != 3;
-  int32_t n_fslots = 0;
-  if (fused_possible && tfus != tseq) n_fslots = make_items(tfus, fitems, fmulti);
+  p->n_blocks = t.n_blocks;
+  if (t.n_blocks == 0) return WG_OK;  // no dense block, or a repeated entry: the gather kernel (get_tile_plan)
   p->n_plan = n_plan;
   p->col_limit = col_limit;
-  p->n_blocks = (int32_t)bct.size();
-  p->n_items = (int32_t)items.size();
-  p->n_multi = (int32_t)multi.size();
-  p->n_slots = n_slots;
-  p->dense_nnz = dense;
-  int rc = upload(&p->bct, bct);
-  if (!rc) rc = upload(&p->bmask, bmask);
-  if (!rc) rc = upload(&p->items, items);
-  if (!rc) rc = upload(&p->multi, multi);
-  if (fitems.empty()) {  // the fused launch walks the same items
+  p->n_items = (int32_t)t.items.size();
+  p->n_multi = (int32_t)t.multi.size();
+  p->n_slots = t.n_slots;
+  p->dense_nnz = t.dense_nnz;
+  int rc = upload(&p->bct, t.bct);
+  if (!rc) rc = upload(&p->bmask, t.bmask);
+  if (!rc) rc = upload(&p->items, t.items);
+  if (!rc) rc = upload(&p->multi, t.multi);
+  if (t.fitems.empty()) {  // the fused launch walks the same items
     p->fitems = p->items;
     p->fmulti = p->multi;
     p->n_fitems = p->n_items;
     p->n_fmulti = p->n_multi;
     p->n_fslots = p->n_slots;
   } else {
-    if (!rc) rc = upload(&p->fitems, fitems);
-    if (!rc) rc = upload(&p->fmulti, fmulti);
-    p->n_fitems = (int32_t)fitems.size();
-    p->n_fmulti = (int32_t)fmulti.size();
-    p->n_fslots = n_fslots;
+    if (!rc) rc = upload(&p->fitems, t.fitems);
+    if (!rc) rc = upload(&p->fmulti, t.fmulti);
+    p->n_fitems = (int32_t)t.fitems.size();
+    p->n_fmulti = (int32_t)t.fmulti.size();
+    p->n_fslots = t.n_fslots;
   }
-  if (!rc) rc = upload(&p->tcol, tcol);
-  if (!rc) rc = upload(&p->tsplit, tsplit);
-  if (rc) return rc;
-  char buf[256];
-  snprintf(buf, sizeof(buf), "tiles: %d dense blocks (%dx32, >= %d entries) hold %lld of %lld entries (%.1f %%); %d items, %d split row blocks (fused launch: %d items, %d split)\n",
-           p->n_blocks, kTR, th, (long long)dense, (long long)nnz, nnz ? 100.0 * dense / nnz : 0.0, p->n_items, p->n_multi,
-           p->n_fitems, p->n_fmulti);
-  p->text = buf;
-  return WG_OK;
+  if (!rc) rc = upload(&p->tcol, t.tcol);
+  if (!rc) rc = upload(&p->tsplit, t.tsplit);
+  if (rc) p->release();
+  else p->text = std::move(t.text);
+  return rc;
 }
 
 }  // namespace
 
 void TilePlan::release() {
-  (void)hipFree(bct);
-  (void)hipFree(bmask);
-  if (fitems != items) (void)hipFree(fitems);
-  if (fmulti != multi) (void)hipFree(fmulti);
-  (void)hipFree(items);
-  (void)hipFree(multi);
-  fitems = nullptr;
-  fmulti = nullptr;
-  (void)hipFree(tcol);
-  (void)hipFree(tsplit);
-  (void)hipFree(part);
-  (void)hipFree(slots);
-  bct = nullptr;
-  bmask = nullptr;
-  items = nullptr;
-  multi = nullptr;
-  tcol = nullptr;
-  tsplit = nullptr;
-  part = nullptr;
-  slots = nullptr;
+  if (fitems == items) fitems = nullptr;  // the fused launch's lists may be the sequential ones
+  if (fmulti == multi) fmulti = nullptr;
+  free_all(bct, bmask, items, multi, fitems, fmulti, tcol, tsplit, part, slots);
   width = 0;
 }
 

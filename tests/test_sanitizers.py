@@ -3,8 +3,10 @@ oracle (oracle/wats_chain.c, the full-size parity checker) built with
 AddressSanitizer + UndefinedBehaviorSanitizer (`make -C oracle asan`) and run on
 every golden fixture -- empty, single-node, self-loop-only, directed weighted
 graphs with isolated nodes -- and on wider random inputs, bit for bit against
-the fixtures; and the C99 consumer of include/wats_hip.h instrumented the same
-way against the shipped library's argument-validation paths.  CPU only (the GPU
+the fixtures; the C99 consumer of include/wats_hip.h instrumented the same
+way against the shipped library's argument-validation paths; and the host
+planners of the step kernels' tables (csrc/plan_host.cpp) with their
+stand-alone checker (tests/c/plan_check.cpp).  CPU only (the GPU
 kernels have their own bounds-checked variant, tools/debug_suite.sh)."""
 import os
 import shutil
@@ -82,4 +84,23 @@ def test_c_abi_consumer_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
     assert out.returncode == 0, out.stderr[-4000:]
+    assert out.stdout.startswith("ok")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_host_planners_under_asan_ubsan(tmp_path):
+    """csrc/plan_host.cpp (the wave, SELL, padded-CSR, segment and tile tables the step kernels read) built
+    without the HIP runtime and run on small graphs holding every branch, each table decoded the way its
+    kernel decodes it (tests/c/plan_check.cpp)."""
+    csrc = os.path.join(REPO, "efficient-gnn_amd", "csrc")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    exe = str(tmp_path / "plan_check_asan")
+    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I",
+                    os.path.join(rocm, "include"), "-I", os.path.join(REPO, "include"), "-I", csrc,
+                    os.path.join(REPO, "tests", "c", "plan_check.cpp"), os.path.join(csrc, "plan_host.cpp"),
+                    "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
     assert out.stdout.startswith("ok")
