@@ -11,7 +11,8 @@ Public surface (reference names):
     WATS  (calibrator), NormalizedLaplacian (device L_hat handle).
 Section 8(f): SparseCompatibleGCN / RowNormalizedAdjacency (the base model's
 propagation as a HIP SpMM), EdgeProbe / target_flip_scores / toggle_edges
-(its gradient at edge positions and the attack's flip, HIP SDDMM), metrics
+(its gradient at edge positions and the attack's flip, HIP SDDMM),
+edge_index_to_csr / DeviceCSR (edge_index to canonical CSR on the device), metrics
 (device ECE).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
@@ -40,5 +41,6 @@ from .gcn import (  # noqa: F401
     toggle_edges,
 )
 from .head import wats_head  # noqa: F401
+from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
 
 __version__ = "0.1.0"

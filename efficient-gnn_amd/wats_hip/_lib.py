@@ -18,6 +18,10 @@ WG_FLAG_NO_REORDER = 1
 WG_FLAG_TRANSPOSE = 2
 WG_FLAG_KEEP_COLUMN_ORDER = 4
 WG_FLAG_CALLER_TIES = 8
+WG_COO_SYMMETRIC = 1
+WG_COO_SUM = 2
+WG_COO_LOOPS_REMOVE = 4
+WG_COO_LOOPS_ONE = 8
 
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32
@@ -79,6 +83,9 @@ SIGNATURES = {
     "wg_spmm": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wg_sddmm": (ctypes.c_int, [c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wg_rowdot": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wg_coo_capacity": (ctypes.c_int, [c_i64, c_i64, c_u32, ctypes.POINTER(c_i64)]),
+    "wg_coo_to_csr": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_u32, c_vp, c_vp, c_vp, c_i64,
+                                     ctypes.POINTER(c_i64), c_vp]),
     "wg_wats_head_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 8 + [c_vp]),
     "wg_wats_head_workspace": (ctypes.c_int, [c_i64, c_i64, c_i32, ctypes.POINTER(c_i64)]),
     "wg_wats_head_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 15 + [c_vp]),

@@ -258,6 +258,23 @@ class RowNormalizedAdjacency:
         return cls(A.shape[0], torch.from_numpy(A.indptr.astype(np.int64)),
                    torch.from_numpy(A.indices.astype(np.int32)), torch.from_numpy(A.data.astype(np.float32)), **kw)
 
+    @classmethod
+    def from_graph(cls, g, **kw):
+        """From a ``wats_hip.graphgen.CSRGraph`` or a ``wats_hip.ingest.DeviceCSR``."""
+        import numpy as np
+        to_t = lambda a, dt: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=dt))
+        return cls(g.n, to_t(g.indptr, np.int64), to_t(g.indices, np.int32),
+                   None if g.values is None else to_t(g.values, np.float32), **kw)
+
+    @classmethod
+    def from_edge_index(cls, edge_index, num_nodes: int | None = None, weights=None, *, duplicates: str = "one",
+                        symmetric: bool = False, self_loops: str = "keep", convention: str | None = None, **kw):
+        """From a (2, E) ``edge_index``, ingested on the device (``wats_hip.ingest.edge_index_to_csr``)."""
+        from .ingest import edge_index_to_csr
+        g = edge_index_to_csr(edge_index, num_nodes, weights, duplicates=duplicates, symmetric=symmetric,
+                              self_loops=self_loops, convention=convention, device=kw.get("device"))
+        return cls.from_graph(g, **kw)
+
     def __matmul__(self, x: torch.Tensor) -> torch.Tensor:
         return propagate(self, x)
 

@@ -63,8 +63,8 @@ def dense_to_csr(adj: torch.Tensor):
 class NormalizedLaplacian:
     """``L_hat = L_sym - I`` of a graph, materialised on one GPU.
 
-    Build with :meth:`from_csr`, :meth:`from_dense`, :meth:`from_scipy` or
-    :func:`compute_normalized_laplacian`.  For a row shard (multi-GPU) the
+    Build with :meth:`from_csr`, :meth:`from_dense`, :meth:`from_scipy`,
+    :meth:`from_edge_index` or :func:`compute_normalized_laplacian`.  For a row shard (multi-GPU) the
     columns are ``[owned rows | halo rows]`` and ``w_cols`` carries the global
     column degrees (see ``wats_hip.dist``).  ``sort_columns=False`` keeps
     each row's entries in the caller's order (``WG_FLAG_KEEP_COLUMN_ORDER``)
@@ -173,8 +173,17 @@ class NormalizedLaplacian:
 
     @classmethod
     def from_graph(cls, g, **kw):
-        """From a ``wats_hip.graphgen.CSRGraph``."""
+        """From a ``wats_hip.graphgen.CSRGraph`` or a ``wats_hip.ingest.DeviceCSR``."""
         return cls.from_csr(g.indptr, g.indices, g.values, n=g.n, **kw)
+
+    @classmethod
+    def from_edge_index(cls, edge_index, num_nodes: int | None = None, weights=None, *, duplicates: str = "one",
+                        symmetric: bool = False, self_loops: str = "keep", convention: str | None = None, **kw):
+        """From a (2, E) ``edge_index``, ingested on the device (``wats_hip.ingest.edge_index_to_csr``)."""
+        from .ingest import edge_index_to_csr
+        g = edge_index_to_csr(edge_index, num_nodes, weights, duplicates=duplicates, symmetric=symmetric,
+                              self_loops=self_loops, convention=convention, device=kw.get("device"))
+        return cls.from_graph(g, **kw)
 
     # ------------------------------------------------------------------ API
     @property

@@ -405,6 +405,48 @@ int wg_sddmm(int64_t n_pairs, const int32_t* rows, const int32_t* cols, int64_t 
 int wg_rowdot(int64_t n, int64_t F, const float* A, const float* B, float* out, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Section 8(f) rank 1, second half: graph ingestion from an edge list.  The
+ * reference turns edge_index into a dense (N,N) adjacency --
+ *   adj[src, dst] = 1                               (calibration/utils.py:19-25 via
+ *                                                    benchmark_calibration_methods.py:53)
+ *   adj = clamp(adj + adj.t(), 0, 1); adj.fill_diagonal_(1.0)
+ *                                                   (ugca_calib_attack.py:42-47,
+ *                                                    exp/ablation/ugca_full_multi_dataset.py:135-140)
+ * -- and gives the adjacency up above 50 000 nodes (ugca_full_multi_dataset.py:128-133).
+ * wg_coo_to_csr builds the canonical CSR of that matrix from the ids directly.
+ * With A0 the duplicates' result, A1 the symmetrised and A2 the final matrix:
+ *   duplicates  default: A0[i,j] = 1 if any edge (i,j) is present;
+ *               WG_COO_SUM: A0[i,j] = sum of weights (NULL = 1) over the edges (i,j)
+ *   WG_COO_SYMMETRIC     default mode: A1 = max(A0, A0^T); WG_COO_SUM: A1 = A0 + A0^T
+ *                        (the diagonal doubles, as adj + adj.t() does)
+ *   WG_COO_LOOPS_REMOVE  the diagonal becomes 0;  WG_COO_LOOPS_ONE: it becomes 1 on every row
+ * Output: the entries of A2 that are != 0 -- indptr int64 [n + 1], indices int32
+ * ascending in each row without duplicates, values float32 (may be NULL without
+ * WG_COO_SUM: every value is 1).  WG_COO_SUM sums are float64, the forward
+ * contributions in input order, then the mirrored ones in input order, rounded
+ * once to float32; no float atomics: the same input gives the same bits.
+ * src / dst: n_edges ids of id_bytes (4 | 8) each, on the device.  An id outside
+ * [0, n) is WG_ERR_INVALID with the count in the message (the outputs are then
+ * unspecified; no bad id is ever used as an index).  indices / values hold
+ * `capacity` >= wg_coo_capacity entries (host only, no device work:
+ * n_edges * (2 if symmetric) + (n if WG_COO_LOOPS_ONE); WG_ERR_UNSUPPORTED when
+ * that or n exceeds int32).  Every argument is checked before any device call.
+ * Synchronous: temporary memory is allocated and freed inside the call, the work
+ * runs on `stream`, one stream sync returns nnz and the bad-id count.
+ * ---------------------------------------------------------------------- */
+#define WG_COO_SYMMETRIC 1u
+#define WG_COO_SUM 2u            /* default: presence ("one") */
+#define WG_COO_LOOPS_REMOVE 4u
+#define WG_COO_LOOPS_ONE 8u      /* both loop flags: WG_ERR_INVALID */
+int wg_coo_capacity(int64_t n, int64_t n_edges, uint32_t flags, int64_t* capacity_host);
+int wg_coo_to_csr(int64_t n, int64_t n_edges, const void* src, const void* dst,
+                  int32_t id_bytes /* 4 | 8 */,
+                  const float* weights /* NULL = 1; must be NULL without WG_COO_SUM */,
+                  uint32_t flags, int64_t* indptr, int32_t* indices,
+                  float* values /* may be NULL without WG_COO_SUM */, int64_t capacity,
+                  int64_t* nnz_host, void* stream);
+
+/* -------------------------------------------------------------------------
  * Section 8(f)-3: the WATS temperature head, fused.  Reference
  * calibration/WATS.py:101-105 (net = Linear(F,16) - ReLU - Linear(16,1)) and
  * :124-130 (T = log(exp(net(H)) + 1.1); out = log_softmax(logits / T)).
