@@ -12,7 +12,8 @@ Public surface (reference names):
 Section 8(f): SparseCompatibleGCN / RowNormalizedAdjacency (the base model's
 propagation as a HIP SpMM), EdgeProbe / target_flip_scores / toggle_edges
 (its gradient at edge positions and the attack's flip, HIP SDDMM),
-edge_index_to_csr / DeviceCSR (edge_index to canonical CSR on the device), metrics
+RowNormalizedAdjacency.with_flips / FlippedAdjacency (a flipped graph as a view
+of its parent's operators, committed to CSR without a rebuild), edge_index_to_csr / DeviceCSR (edge_index to canonical CSR on the device), metrics
 (device ECE).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
@@ -42,5 +43,6 @@ from .gcn import (  # noqa: F401
 )
 from .head import wats_head  # noqa: F401
 from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
+from .flips import FlippedAdjacency  # noqa: F401
 
 __version__ = "0.1.0"

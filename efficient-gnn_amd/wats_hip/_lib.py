@@ -83,6 +83,12 @@ SIGNATURES = {
     "wg_spmm": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wg_sddmm": (ctypes.c_int, [c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wg_rowdot": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "wg_flip_resolve": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wg_flip_rows": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                    c_vp, c_vp, c_vp]),
+    "wg_flip_cols": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wg_csr_patch": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_i64, ctypes.POINTER(c_i64), c_vp]),
     "wg_coo_capacity": (ctypes.c_int, [c_i64, c_i64, c_u32, ctypes.POINTER(c_i64)]),
     "wg_coo_to_csr": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_u32, c_vp, c_vp, c_vp, c_i64,
                                      ctypes.POINTER(c_i64), c_vp]),

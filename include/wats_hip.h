@@ -405,6 +405,61 @@ int wg_sddmm(int64_t n_pairs, const int32_t* rows, const int32_t* cols, int64_t 
 int wg_rowdot(int64_t n, int64_t F, const float* A, const float* B, float* out, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Edge-flip views of that propagation.  One attack iteration flips an edge of
+ * the dense adjacency -- v = 1 - 2 adj[r,c]; adj[r,c] += v; adj[c,r] += v -- and
+ * evaluates the model on the flipped graph (calib_attack/calib_fga.py:901-913).
+ * The flipped matrix A' differs from A in a few rows, so a view keeps A's
+ * operators and an overlay: n_pos positions sorted by (row, column), grouped by
+ * touched row -- t_rows [n_touched] ascending, seg [n_touched + 1] with
+ * positions [seg[i], seg[i+1]) in row t_rows[i] (none empty), cols [n_pos] --
+ * each with a_old (A's entry, 0 if absent), a_new (A''s entry) and base_pos
+ * (its index in A's indices, or -1).  A is a canonical CSR: indptr int64
+ * [n + 1], indices int32 ascending in each row, values float32 or NULL (ones).
+ * wg_flip_resolve: a_old and base_pos of every position (binary search in the
+ *   row) and row_sum [n_touched], the float64 sum of each touched row's values
+ *   (its length when values is NULL), lanes striding the row, then a fixed
+ *   shuffle tree.
+ * wg_flip_rows (forward): overwrites the touched rows of y = adj_norm(A) @ x
+ *   (wg_spmm of A's handle) with those of adj_norm(A') @ x:
+ *     y[r,:] = sum over the entries a'_rc != 0 of row r of float32(a'_rc / deg_new[i]) * x[c,:]
+ *   in float64, deg_new [n_touched] the new degrees (0 -> 1).  A row without
+ *   entries gives exactly 0.
+ * wg_flip_cols (backward): the overlay by column -- c_cols [n_cols] distinct,
+ *   cseg [n_cols + 1], and per position in (column, row) order its row, a_new,
+ *   a_old and the row's new degree deg_new [n_pos].  After wg_spmm of A's
+ *   transposed handle on g with each touched row scaled by deg / deg',
+ *     gx[c,:] = float32(gx[c,:] + sum_p ((a_new - a_old) / deg_new) * g[rows[p],:])
+ *   in float64 in ascending row order (a removed entry cancels to rounding).
+ * wg_csr_patch (commit): the canonical CSR of A' -- columns ascending, no
+ *   stored zero -- from A's CSR and the overlay: new row lengths, one exclusive
+ *   scan, one copy pass; no row is sorted again.  out_indices / out_values hold
+ *   `capacity` >= nnz + n_pos entries, out_indptr n + 1.  Synchronous: one
+ *   temporary allocation, freed inside the call; one stream sync returns the
+ *   new nnz.  WG_ERR_UNSUPPORTED when n or nnz + n_pos exceeds int32.
+ * Ids are trusted (checked on the device in the bounds-checked variant only);
+ * every other argument is checked before any device work.  x, y, g, gx are
+ * (n, F) row-major.  Float64 sums in a fixed order, no float atomics: bitwise
+ * reproducible.  n_pos == 0 is WG_OK with no launch (wg_csr_patch: a copy).
+ * The first three are asynchronous, allocate nothing and may be captured.
+ * ---------------------------------------------------------------------- */
+int wg_flip_resolve(int64_t n, const int64_t* indptr, const int32_t* indices, const float* values,
+                    int64_t n_touched, const int32_t* t_rows, const int64_t* seg, int64_t n_pos,
+                    const int32_t* cols, float* a_old, int64_t* base_pos, double* row_sum,
+                    void* stream);
+int wg_flip_rows(int64_t n, const int64_t* indptr, const int32_t* indices, const float* values,
+                 int64_t n_touched, const int32_t* t_rows, const int64_t* seg, int64_t n_pos,
+                 const int32_t* cols, const float* a_new, const int64_t* base_pos,
+                 const float* deg_new, int64_t F, const float* x, float* y, void* stream);
+int wg_flip_cols(int64_t n, int64_t n_cols, const int32_t* c_cols, const int64_t* cseg,
+                 int64_t n_pos, const int32_t* rows, const float* a_new, const float* a_old,
+                 const float* deg_new, int64_t F, const float* g, float* gx, void* stream);
+int wg_csr_patch(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                 const float* values, int64_t n_touched, const int32_t* t_rows, const int64_t* seg,
+                 int64_t n_pos, const int32_t* cols, const float* a_new, const int64_t* base_pos,
+                 int64_t* out_indptr, int32_t* out_indices, float* out_values, int64_t capacity,
+                 int64_t* nnz_host, void* stream);
+
+/* -------------------------------------------------------------------------
  * Section 8(f) rank 1, second half: graph ingestion from an edge list.  The
  * reference turns edge_index into a dense (N,N) adjacency --
  *   adj[src, dst] = 1                               (calibration/utils.py:19-25 via
