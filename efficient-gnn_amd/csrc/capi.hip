@@ -225,6 +225,9 @@ int wg_laplacian_tune(wg_laplacian_t L, const char* key, int64_t value) {
     L->tune.team = (int32_t)value;
     return WG_OK;  // launch-time choice (the wave table is built with the plan on first use)
 
+  } else if (!strcmp(key, "team_spec")) {
+    L->tune.team_spec = value ? 1 : 0;
+    return WG_OK;  // launch-time choice
   } else if (!strcmp(key, "team_tail")) {
     if (value < 0) return fail(WG_ERR_INVALID, "team_tail must be >= 0");
     L->tune.team_tail = value;
@@ -326,8 +329,8 @@ const char* wg_laplacian_describe(wg_laplacian_t L, int64_t F) {
     return (int)std::count_if(h.begin(), h.end(), [](uint32_t v) { return v != 0; });
   };
   if (p->team.wd) {  // the independent-wave step kernel's table, once a step has built it (team.hip)
-    snprintf(buf, sizeof(buf), "team: waves=%d long_rows=%d part_slots=%d max_parts=%d npot_rows=%d pending_arrivals=%d\n",
-             p->team.n_waves, p->team.n_long, p->team.n_slots, p->team.max_parts, p->team.npot_rows,
+    snprintf(buf, sizeof(buf), "team: waves=%d long_rows=%d part_slots=%d max_parts=%d npot_rows=%d spec=%d pending_arrivals=%d\n",
+             p->team.n_waves, p->team.n_long, p->team.n_slots, p->team.max_parts, p->team.npot_rows, L->tune.team_spec,
              pending(p->team.warr, p->team.n_long));
     g_text += buf;
   }

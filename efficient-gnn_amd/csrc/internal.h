@@ -263,6 +263,8 @@ struct Tuning {
   int32_t team = 1;          // padded-CSR steps as independent waves (team.hip cheb_team4_kernel); 7 .. 13:
                              // register-budget / turn-size variants (team.hip launch_team4; all time the same)
                              // instead of Clenshaw's 3; 0 = Clenshaw
+  int32_t team_spec = 1;     // team.hip: the Clenshaw-u chain's launches on straight-line kernels, one per chain
+                             // mode (team_dev.h team_wave_spec); 0 = the generic kernel for every launch
   int32_t fold = 1;          // wg_wavelet_features on the team kernel: no permute-in pass (the first launch
                              // gathers the caller's X0 scaled by dinv, writes the internal X0, finishes
                              // the closed-form rows; team.hip cheb_team4_first_kernel); 2 = a pass writes
@@ -485,7 +487,8 @@ int build_pcol(wg_laplacian_s* L);
 int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32_t* dcol,
                      const int32_t* drsplit, int order, TeamPlan* tp);
 struct StepArgs;
-int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, hipStream_t stream,
+// spec: the chain's own launches on their straight-line kernels (tuning key team_spec)
+int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, int spec, hipStream_t stream,
                  const TeamFirst* first = nullptr);
 int build_team_first(wg_laplacian_s* L, TeamPlan* tp);
 // the value-free VEC-4 gathers on the padded CSR apply to an F-wide (internal width) signal

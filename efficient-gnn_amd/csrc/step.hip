@@ -785,7 +785,7 @@ int launch_step(wg_laplacian_s* L, int32_t k, int64_t F, const float* xm1, const
           a.x0c = cl->x0c;
           a.x0i = cl->x0i;
           a.perm_in = L->perm;
-          if (int rc2 = launch_team4(plan->team, a, L->tune.team, stream, &cl->closed)) return rc2;
+          if (int rc2 = launch_team4(plan->team, a, L->tune.team, L->tune.team_spec, stream, &cl->closed)) return rc2;
           continue;
         }
         if (tsum) {
@@ -798,7 +798,7 @@ int launch_step(wg_laplacian_s* L, int32_t k, int64_t F, const float* xm1, const
             continue;
           }
         }
-        if (int rc2 = launch_team4(plan->team, a, L->tune.team, tail_stream)) return rc2;
+        if (int rc2 = launch_team4(plan->team, a, L->tune.team, L->tune.team_spec, tail_stream)) return rc2;
         continue;
       }
       if (g4 && !hyb) {

@@ -521,6 +521,7 @@ __device__ __forceinline__ void accumulate_vidx1(const StepArgs& a, int32_t e0, 
 }
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
 // Value-free gathers (unweighted graphs, u = b * dinv), VEC = 4, on the padded CSR: a sub-group
 // walks the 4-entry chunks q, q + step, ... of its range [q, e1) (multiples of 4), CPT chunks per
@@ -751,6 +752,73 @@ __device__ __forceinline__ void accumulate_sell(const StepArgs& a, int2 wm, int 
 #pragma unroll
     for (int u = 0; u < 4; ++u) x[u] = gather(cc[u]);
     if constexpr (FIRST) scale_chunk(rd, off, x);
+    sum_turn(x, 4, acc);
+  }
+}
+
+// ---- the straight-line form of the team step (team_dev.h team_wave_spec) ----
+//
+// A load that only some lanes (or some launches' waves) need is issued by every lane as a raw buffer
+// load, the others at an offset past the buffer's end: it returns 0 and makes no memory request (as a
+// pad id's gather).  The loaded registers are then defined on one path, so no branch joins on them:
+// the generic kernel's copies at such joins each drew an s_waitcnt vmcnt(0), one full memory round
+// trip per operand row in front of the wave's first id load.
+constexpr uint32_t kOobOff = 0xFFFFFFF0u;
+constexpr int kBufFlags = 0x00020000;
+
+template <class T>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_of(const T* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p), 0, (int)bytes, kBufFlags);
+}
+
+// accumulate_sell<2> on ids whose first turn (c0, c1: chunks 0 and 1 at byte offset `off`) is
+// already in flight: the same gathers and sums in the same order.  Every lane runs it; a lane with
+// `on` false (outside the wave's rows) loads past the buffers' ends, so its ids read 0 and its gathers
+// and sums are of zeros with no memory request: no branch around the loop, whose loads would sink
+// into it.  Chunks past the sub-group's count ny are not loaded (the single-chunk wave's second
+// chunk, the look-ahead of the last turn): wave-uniform branches around the loads, whose registers
+// start as zeros, not as copies of loaded ones (a copy would wait for its source).
+// once(): called one time, after the first turn's gathers are issued (work that hides behind them);
+// never when there is no turn (ny == 0).
+template <class Once>
+__device__ __forceinline__ void accumulate_sell_from(const StepArgs& a, u32x4_t c0, u32x4_t c1, uint32_t off,
+                                                     uint32_t cstep, int ny, int fs, bool on, double (&acc)[4],
+                                                     Once&& once) {
+  const __amdgpu_buffer_rsrc_t rs = buf_of(a.xm1, a.u_bytes);
+  const __amdgpu_buffer_rsrc_t ri = buf_of(a.sell, 0x7fffffffu);
+  const uint32_t rb = (uint32_t)a.ld * 4u;
+  const uint32_t lo = on ? (uint32_t)fs * 16u : kOobOff;  // id 0 of a lane that is off: past the end
+  auto ld = [&](uint32_t o) {  // volatile (aux bit 31): not sunk to its use (accumulate_u4)
+    return __builtin_amdgcn_raw_buffer_load_b128(ri, on ? o : kOobOff, 0, (int)(1u << 31));
+  };
+  auto gather = [&](uint32_t c) -> u32x4_t {
+    return __builtin_amdgcn_raw_buffer_load_b128(rs, __umul24(c, rb) + lo, 0, 0);
+  };
+  bool pending = true;
+  const int pairs = ny >> 1;
+  for (int t = 0; t < pairs; ++t) {
+    off += 2 * cstep;
+    u32x4_t n0 = {0u, 0u, 0u, 0u}, n1 = n0;  // (a turn that does not exist reads neither)
+    if (2 * t + 2 < ny) n0 = ld(off);
+    if (2 * t + 3 < ny) n1 = ld(off + cstep);
+    const uint32_t cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+    u32x4_t x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = gather(cc[u]);
+    if (pending) {
+      once();
+      pending = false;
+    }
+    sum_turn(x, 8, acc);
+    c0 = n0;
+    c1 = n1;
+  }
+  if (ny & 1) {  // the last, single chunk
+    const uint32_t cc[4] = {c0.x, c0.y, c0.z, c0.w};
+    u32x4_t x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = gather(cc[u]);
+    if (pending) once();
     sum_turn(x, 4, acc);
   }
 }

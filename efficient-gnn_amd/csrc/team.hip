@@ -17,6 +17,9 @@
 //     split rows, per wave instead of per workgroup).
 // Every wave reads its column ids in SELL order (accumulate_sell: one coalesced id read per turn,
 // pads are dropped loads), so the kernel has no LDS, no barrier and a lean register budget.
+// The launches of a Clenshaw chain on u after its first run cheb_team4_spec_kernel, the same wave with
+// the launch's mode fixed at compile time and its loads issued on one straight path (team_dev.h
+// team_wave_spec, tuning key team_spec); every other launch runs cheb_team4_kernel.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -42,6 +45,13 @@ __global__ __launch_bounds__(256, 6) void cheb_team4_first_kernel(TeamArgs t) {
   const int w = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (w < t.n_waves) team_wave<false, 2, GX>(t, w);
   else if (w < t.n_waves + t.n_closed_waves) closed_wave(t, w - t.n_waves);
+}
+
+// the chain's launches after the first, one straight-line kernel per mode (team_dev.h team_wave_spec)
+template <class M>
+__global__ __launch_bounds__(256, 6) void cheb_team4_spec_kernel(TeamArgs t) {
+  const int w = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (w < t.n_waves) team_wave_spec<M>(t, w);
 }
 
 }  // namespace
@@ -97,7 +107,8 @@ int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32
   return rc;
 }
 
-int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, hipStream_t stream, const TeamFirst* first) {
+int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, int spec, hipStream_t stream,
+                 const TeamFirst* first) {
   TeamArgs t{};
   t.a = a;
   t.wd = tp.wd;
@@ -132,6 +143,15 @@ int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, hipStream_t
   }
   if (tp.n_waves <= 0) return WG_OK;
   const dim3 grid((unsigned)ceil_div(tp.n_waves, 4)), block(256);
+  // the chain's own launches as straight-line kernels (tuning key team_spec); anything else generic
+  const TeamMode mode = spec && variant == 1 ? team_mode_of(t.a) : kTeamGeneric;
+  if (mode != kTeamGeneric) {
+    if (mode == kTeamMid) hipLaunchKernelGGL(cheb_team4_spec_kernel<TeamMid>, grid, block, 0, stream, t);
+    else if (mode == kTeamMidNoPrev) hipLaunchKernelGGL(cheb_team4_spec_kernel<TeamMidNoPrev>, grid, block, 0, stream, t);
+    else hipLaunchKernelGGL(cheb_team4_spec_kernel<TeamFinal>, grid, block, 0, stream, t);
+    WG_LAUNCH_CHECK();
+    return WG_OK;
+  }
   switch (variant) {
     case 7: hipLaunchKernelGGL((cheb_team4_kernel<7, false>), grid, block, 0, stream, t); break;
     case 8: hipLaunchKernelGGL((cheb_team4_kernel<8, false>), grid, block, 0, stream, t); break;

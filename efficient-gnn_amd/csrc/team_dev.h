@@ -177,5 +177,217 @@ __device__ __forceinline__ void team_wave(const TeamArgs& t, int w) {
   }
 }
 
+// ---- the chain's own launches as straight-line kernels (tuning key team_spec) ----
+//
+// The Clenshaw chain on u (capi.hip wavelet_chain) makes, after its folded first launch, three kinds
+// of launch.  A mode fixes every launch-uniform flag of one kind at compile time (team_mode_of picks
+// it from StepArgs; any other combination, the first launch included, runs team_wave): clen, uin = 1,
+// x0 and iso present, k = 2, the sc1 T_k store (nt 8), no tsum / phase / probe / out-of-table checks.
+//   kClen   1 = a step (u_k stored with sc1), 2 = the final step (S and H at caller rows out_perm)
+//   kPrev   xm2 present and holding u (uprev)
+struct TeamMid { static constexpr int kClen = 1; static constexpr bool kPrev = true; };
+struct TeamMidNoPrev { static constexpr int kClen = 1; static constexpr bool kPrev = false; };
+struct TeamFinal { static constexpr int kClen = 2; static constexpr bool kPrev = true; };
+
+enum TeamMode { kTeamGeneric = 0, kTeamMid, kTeamMidNoPrev, kTeamFinal };
+
+inline TeamMode team_mode_of(const StepArgs& a) {
+#if defined(WG_TIMING_PROBES) || defined(WG_DEBUG_BOUNDS)
+  (void)a;
+  return kTeamGeneric;
+#else
+  if (!a.clen || !a.uin || a.val || a.k != 2 || a.first || a.tsum || a.phase || a.probe || (a.nt & 12) != 8 ||
+      !a.x0 || !a.iso || !a.dinv || !a.sell)
+    return kTeamGeneric;
+  const bool prev = a.xm2 != nullptr;
+  if (prev != (a.uprev != 0)) return kTeamGeneric;
+  if (a.clen == 1 && a.uout && a.xk) return prev ? kTeamMid : kTeamMidNoPrev;
+  if (a.clen == 2 && !a.uout && !a.xk && prev && a.S && a.H && a.out_perm && a.S_out) return kTeamFinal;
+  return kTeamGeneric;
+#endif
+}
+
+// a row's epilogue operands as loaded registers (raw bits; masked lanes hold 0)
+struct EpiRegs {
+  u32x4_t prev, x0;
+  uint32_t dlo, dhi;  // dinv (float64)
+  uint32_t iso;
+  uint32_t orow;      // the final step: out_perm[row]
+};
+
+// every lane issues the loads, lanes with `on` false past the buffers' ends (no request); nothing here
+// waits
+template <class M>
+__device__ __forceinline__ void epi_issue(const StepArgs& a, int row, int fs, bool on, EpiRegs& in) {
+  const uint32_t r = (uint32_t)row;
+  const uint32_t off = on ? r * ((uint32_t)a.ld * 4u) + (uint32_t)fs * 16u : kOobOff;
+  in.orow = 0;
+  if constexpr (M::kClen == 2)
+    in.orow = __builtin_amdgcn_raw_buffer_load_b32(buf_of(a.out_perm, 0x7fffffffu), on ? r * 4u : kOobOff, 0, 0);
+  in.iso = __builtin_amdgcn_raw_buffer_load_b8(buf_of(a.iso, 0x7fffffffu), on ? r : kOobOff, 0, 0);
+  const u32x2_t d = __builtin_amdgcn_raw_buffer_load_b64(buf_of(a.dinv, 0x7fffffffu), on ? r * 8u : kOobOff, 0, 0);
+  in.dlo = d.x;
+  in.dhi = d.y;
+  if constexpr (M::kPrev) in.prev = __builtin_amdgcn_raw_buffer_load_b128(buf_of(a.xm2, a.u_bytes), off, 0, 0);
+  else in.prev = u32x4_t{0u, 0u, 0u, 0u};
+  in.x0 = __builtin_amdgcn_raw_buffer_load_b128(buf_of(a.x0, a.u_bytes), off, 0, 0);
+}
+
+// step_epilogue's arithmetic for one mode, operation for operation as the generic kernel compiles it
+// (contraction off and the fused operations written out, so S and H keep their bits):
+//   acc *= -dinv;  isolated row: acc = fma(-1/dinv, u_own, acc)
+//   t = fma(-1/dinv, prev, fma(ck, X0, cacc * acc));  u = t * dinv
+// rinv: 1 / dinv (kPrev modes; the others divide in the isolated row's branch)
+template <class M>
+__device__ __forceinline__ void epilogue_spec(const StepArgs& a, int row, int fs, double (&acc)[4],
+                                              const EpiRegs& in, double rinv, int lane0) {
+#pragma clang fp contract(off)
+  const int64_t off = (int64_t)row * a.ld + (int64_t)fs * 4;
+  const double dinv = __hiloint2double((int)in.dhi, (int)in.dlo);
+  const float x0[4] = {__uint_as_float(in.x0.x), __uint_as_float(in.x0.y), __uint_as_float(in.x0.z),
+                       __uint_as_float(in.x0.w)};
+  const float prev[4] = {__uint_as_float(in.prev.x), __uint_as_float(in.prev.y), __uint_as_float(in.prev.z),
+                         __uint_as_float(in.prev.w)};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = acc[j] * -dinv;
+  if (in.iso) {  // L_hat_ii = -1: the own row of u, as b
+    float x[4];
+    load_vec<4>(a.xm1 + off, x);
+    const double xs = M::kPrev ? rinv : 1.0 / dinv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = fma(-xs, (double)x[j], acc[j]);
+  }
+  double t[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    t[j] = fma(a.ck, (double)x0[j], a.cacc * acc[j]);
+    if constexpr (M::kPrev) t[j] = fma(-rinv, (double)prev[j], t[j]);
+  }
+  if constexpr (M::kClen == 1) {
+    double u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = t[j] * dinv;
+    store_vec_sc1<4>(a.xk + off, u);
+  } else {  // the final step: S = t and H = S / (|S|_1 + 1e-8) at the caller's row
+    const int64_t oo = (int64_t)(int32_t)in.orow * a.ld + (int64_t)fs * 4;
+    store_vec<4>(a.S_out + oo, t);
+    double part = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part += fabs(t[j]);
+    double tot = 0.0;
+    for (int q = 0; q < a.LF; ++q) tot += __shfl(part, lane0 + q, 64);
+    const double den = tot + 1e-8;
+    double h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = t[j] / den;
+    store_vec<4>(a.H + oo, h);
+  }
+}
+
+// team_wave for one chain mode.  Issue order: descriptor; the first turn's ids; the row's epilogue
+// operands (all in flight together; vmcnt retires in order, so the ids go first and the first wait is
+// the one the gathers need); the gather loop, a step's 1 / dinv computed behind the first turn's
+// gathers; the epilogue.  A long row's last arriver issues its first four parts' partials, then the
+// operands, before the first add (part order kept).
+template <class M>
+__device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
+  const StepArgs& a = t.a;
+  const int4 d0 = t.wd[2 * w];  // uniform address: a scalar load
+  const int lane = threadIdx.x & 63;
+  const int LF = a.LF;
+  const int G = 64 / LF;
+  const int sg = lane / LF;
+  const int fs = lane - sg * LF;
+  const int LN = d0.w & 0xff;
+  const int tpw = (d0.w >> 8) & 0xff;
+  const bool part = (d0.w >> 16) & 1;
+  const int team = sg / LN;
+  const int ns = sg - team * LN;
+  const int row = d0.z + team;  // rows are 24-bit ids (gather4_applies)
+  const bool active = sg < G && team < tpw;
+  const int ny = d0.y;
+  const uint32_t cstep = (uint32_t)G * 16u;
+  const uint32_t off0 = ((uint32_t)d0.x + (uint32_t)sg) * 16u;
+  const __amdgpu_buffer_rsrc_t ri = buf_of(a.sell, 0x7fffffffu);
+  const u32x4_t c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, active && ny > 0 ? off0 : kOobOff, 0, (int)(1u << 31));
+  u32x4_t c1 = {0u, 0u, 0u, 0u};  // (a single-chunk wave does not read it)
+  if (ny > 1) c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, active ? off0 + cstep : kOobOff, 0, (int)(1u << 31));
+  EpiRegs in;
+  const bool own = active && ns == 0 && !part;
+  epi_issue<M>(a, row, fs, own, in);
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double rinv = 0.0;
+  // 1 / dinv where it is placed, not hoisted in front of the gathers (dinv itself goes through the
+  // empty asm, so no second copy of it stays live)
+  auto divide = [&](EpiRegs& e) {
+    asm volatile("" : "+v"(e.dlo), "+v"(e.dhi));
+    return 1.0 / __hiloint2double((int)e.dhi, (int)e.dlo);
+  };
+  // behind the first turn's gathers: a step's 1 / dinv (the final launch has no registers to hold it
+  // across the loop within 80)
+  constexpr bool kDivEarly = M::kPrev && M::kClen == 1;
+  auto behind = [&] {
+    if constexpr (kDivEarly) rinv = divide(in);
+  };
+  accumulate_sell_from(a, c0, c1, off0, cstep, ny, fs, active, acc, behind);  // every lane
+  if (ny <= 0) behind();  // no turn to hide it behind
+  if constexpr (M::kPrev && !kDivEarly) rinv = divide(in);
+  reduce_subgroups<4>(acc, LN, LF, team * LN * LF, fs);  // every lane (shuffles)
+  if (!part) {
+    if (own) epilogue_spec<M>(a, row, fs, acc, in, rinv, team * LN * LF);
+    return;
+  }
+  {  // a share of a long row: float64 partial (sc1), drained, then one arrival per wave
+    const int4 d1 = t.wd[2 * w + 1];
+    const int width = LF * 4;
+    if (lane < LF) {
+      double* p = t.wpart + (int64_t)(d1.z + d1.x) * width + lane * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) __hip_atomic_store(p + j, acc[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    int last = 0;
+    if (lane == 0) {  // the arrival that completes the row resets its counter (team_wave)
+      const uint32_t old = __hip_atomic_fetch_add(t.warr + d1.w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      last = old + 1u == (uint32_t)d1.y;
+      if (last) __hip_atomic_store(t.warr + d1.w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    last = __shfl(last, 0, 64);
+    if (!last || lane >= LF) return;
+    // the last arriver: lanes 0 .. LF-1 (fs == lane).  The row's partial slots as one raw buffer that
+    // ends with the row's last part: the first four parts are loaded whole before the first add
+    // (write-through sc1 loads, 32 B per lane and part), parts past the last return 0.0, and a sum that
+    // started from +0.0 is never -0.0, so adding that 0.0 leaves it as it is
+    const __amdgpu_buffer_rsrc_t rp = buf_of(t.wpart + (int64_t)d1.z * width, (uint32_t)d1.y * (uint32_t)width * 8u);
+    constexpr int kSc1Volatile = 16 | (int)(1u << 31);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    auto load_part = [&](int q, u32x4_t& lo, u32x4_t& hi) {
+      const uint32_t o = (uint32_t)q * (uint32_t)width * 8u + (uint32_t)lane * 32u;
+      lo = __builtin_amdgcn_raw_buffer_load_b128(rp, o, 0, kSc1Volatile);
+      hi = __builtin_amdgcn_raw_buffer_load_b128(rp, o + 16u, 0, kSc1Volatile);
+    };
+    auto add_part = [&](const u32x4_t& lo, const u32x4_t& hi) {
+      s[0] += __hiloint2double((int)lo.y, (int)lo.x);
+      s[1] += __hiloint2double((int)lo.w, (int)lo.z);
+      s[2] += __hiloint2double((int)hi.y, (int)hi.x);
+      s[3] += __hiloint2double((int)hi.w, (int)hi.z);
+    };
+    u32x4_t plo[4], phi[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) load_part(u, plo[u], phi[u]);
+    EpiRegs lin;  // the operands with the first batch, behind it (the sums do not wait for them)
+    epi_issue<M>(a, row, lane, true, lin);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) add_part(plo[u], phi[u]);
+    for (int q0 = 4; q0 < d1.y; q0 += 2) {  // rows of more than four parts: two at a time
+      load_part(q0, plo[0], phi[0]);
+      load_part(q0 + 1, plo[1], phi[1]);
+      add_part(plo[0], phi[0]);
+      add_part(plo[1], phi[1]);
+    }
+    epilogue_spec<M>(a, row, lane, s, lin, M::kPrev ? divide(lin) : 0.0, 0);
+  }
+}
+
 }  // namespace
 }  // namespace wg
