@@ -757,7 +757,7 @@ int build_solo_plan(wg_laplacian_s* L, ChainPlan* p, const std::vector<int32_t>&
   if (!rc) rc = upload(&p->swslots, wslots);
   if (!rc) rc = dmalloc(&p->bar, 4);
   if (rc) return rc;
-  WG_HIP_TRY(hipMemset(p->bar, 0, 4 * sizeof(int32_t)));
+  WG_HIP_TRY(dzero(p->bar, 4 * sizeof(int32_t)));
   WG_HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
   WG_HIP_TRY(hipHostMalloc((void**)&p->host_flag, sizeof(int32_t), hipHostMallocMapped));
   *p->host_flag = 0;
@@ -923,8 +923,8 @@ int build_chain_plan(wg_laplacian_s* L, ChainPlan* p) {
   *p->host_flag = 0;
   WG_HIP_TRY(hipHostGetDevicePointer((void**)&p->d_host_flag, p->host_flag, 0));
   p->seen = 0;
-  WG_HIP_TRY(hipMemset(p->bar, 0, 4 * sizeof(int32_t)));
-  WG_HIP_TRY(hipMemset(p->gbuf, 0, 4 * p->ustride * sizeof(uint64_t)));  // tag 0: never a live phase's
+  WG_HIP_TRY(dzero(p->bar, 4 * sizeof(int32_t)));
+  WG_HIP_TRY(dzero(p->gbuf, 4 * p->ustride * sizeof(uint64_t)));  // tag 0: never a live phase's
   char buf[192];
   snprintf(buf, sizeof(buf), "chain1: one launch per chain, %d workers x %d threads, %lld active rows, %lld nonzeros, "
            "%d wave passes, LDS %d B per worker\n", P, kChainThreads, (long long)na, (long long)nnz,

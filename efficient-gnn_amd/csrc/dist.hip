@@ -258,7 +258,14 @@ struct wg_dist_s {
   int64_t** peer_flags = nullptr;     // device array [world]
   IpcPull pull{};
   int64_t F_sig = 0;        // the signal columns of the running chain (<= the exchanged width)
-  int64_t pads_zeroed = 0;  // the width whose halo pad columns the region holds as zeros
+  // the exchanged width at which the halo rows' columns were last cleared before a narrower pull (0 after a
+  // full-width pull).  It records that width, not the columns still zero: a later signal of the same exchanged
+  // width that pulls fewer columns (fpad 16: F = 41 pulls 44 of 48, then F = 37 pulls 40) leaves the columns in
+  // between holding the earlier signal's values.  That is harmless, not prevented: a step is column-wise, so a
+  // stale halo column c >= F_sig reaches column c of the own rows only, which no finalize reads and no peer
+  // needs zero (test_ipc_chain_narrower_pulls_after_nan_calls[fpad16]: an all-NaN F = 44 call, then F = 37, leaves NaN
+  // in halo columns 40 .. 43 during the checked chain).
+  int64_t pads_zeroed = 0;
   // exchange mode "sdma" (wg_dist_ipc_sdma, after wg_dist_ipc_connect): each rank packs the rows
   // its peers asked for into one of two send buffers of its region; the receiver copies each
   // owner's packed block into its halo rows with hipMemcpyAsync on a copy stream (DMA engines
@@ -375,7 +382,7 @@ struct wg_dist_s {
       const bool v4 = (F % 4 == 0) && slot_floats * 4 < ((int64_t)1 << 31);
       // the columns that carry the signal (pad columns beyond them are zero on every owner)
       const int64_t Fr = std::min<int64_t>(F, (F_sig + 3) / 4 * 4);
-      if (v4 && Fr < F && pads_zeroed != F) {  // pad columns of the halo rows (both slots) are never pulled
+      if (v4 && Fr < F && pads_zeroed != F) {  // columns [Fr, F) of the halo rows (both slots) are not pulled: start them at 0
         for (int sl = 0; sl < 2; ++sl)
           WG_HIP_TRY(hipMemsetAsync(region + sl * slot_floats + n_own * F, 0, sizeof(float) * n_halo * F, st));
         pads_zeroed = F;
@@ -748,16 +755,16 @@ int wg_dist_ipc_local(wg_dist_t D, int64_t F_max, void* blob) {
   if (int rc = dmalloc(&D->count, 1)) return rc;
   if (int rc = dmalloc(&D->err, 1)) return rc;
   if (int rc = dmalloc(&D->arrive, 2)) return rc;
-  WG_HIP_TRY(hipMemset(D->arrive, 0, 2 * sizeof(uint32_t)));
+  WG_HIP_TRY(dzero(D->arrive, 2 * sizeof(uint32_t)));
   {
     int dev = 0, nx = 1;
     WG_HIP_TRY(hipGetDevice(&dev));
     if (hipDeviceGetAttribute(&nx, hipDeviceAttributeNumberOfXccs, dev) != hipSuccess || nx < 1) nx = 1;
     D->n_xcc = std::min(nx, 16);
   }
-  WG_HIP_TRY(hipMemset(D->region, 0, bytes));
-  WG_HIP_TRY(hipMemset(D->count, 0, sizeof(int64_t)));
-  WG_HIP_TRY(hipMemset(D->err, 0, sizeof(int32_t)));
+  WG_HIP_TRY(dzero(D->region, bytes));
+  WG_HIP_TRY(dzero(D->count, sizeof(int64_t)));
+  WG_HIP_TRY(dzero(D->err, sizeof(int32_t)));
   hipIpcMemHandle_t h;
   WG_HIP_TRY(hipIpcGetMemHandle(&h, D->region));
   char* out = static_cast<char*>(blob);

@@ -72,6 +72,16 @@ int upload(T** d, const std::vector<T>& h) {
   return WG_OK;
 }
 
+// Zero freshly allocated plan state (arrival counters, barriers, tag buffers) and wait for the fill.  hipMemset on
+// device memory is ordered on the null stream and may return before the fill has run; a kernel launched next on a
+// NON-BLOCKING stream (the sharded chain's own stream, dist.hip) does not wait for the null stream, so a late fill
+// could clear an arrival counter in the middle of that launch: the row then never completes and its counter
+// stays non-zero for every later launch.
+inline hipError_t dzero(void* p, size_t bytes) {
+  const hipError_t e = hipMemset(p, 0, bytes);
+  return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+
 // hipFree every pointer and null it
 template <typename... P>
 void free_all(P*&... p) {

@@ -1002,7 +1002,7 @@ static int build_shard_hub(wg_laplacian_s* L, Lds1Plan* p, int32_t nnz) {
     (void)hipFree(gd);
     return rc;
   }
-  WG_HIP_TRY(hipMemset(p->hcol + nnz, 0, 4 * sizeof(int32_t)));
+  WG_HIP_TRY(dzero(p->hcol + nnz, 4 * sizeof(int32_t)));
   if (nnz > 0)
     hipLaunchKernelGGL(hub_remap_kernel, dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, 0, (int64_t)nnz,
                        (int32_t)n_own, cnt[0], p->hub, ng, gd, L->col, p->hcol);
@@ -1147,7 +1147,7 @@ int get_lds1_plan(wg_laplacian_s* L, bool active_only, Lds1Plan** out) {
   p->nnz = nnz;
   const int64_t ncnt = nb * n + 1;
   if ((rc = dmalloc(&p->brp, ncnt))) return bail(rc);
-  WG_HIP_TRY(hipMemset(p->brp, 0, sizeof(int32_t) * ncnt));
+  WG_HIP_TRY(dzero(p->brp, sizeof(int32_t) * ncnt));
   const dim3 rgrid((unsigned)ceil_div(n, 4));
   hipLaunchKernelGGL(lds1_count_kernel, rgrid, dim3(256), 0, 0, (int32_t)n, (int32_t)nb, L->rowptr, L->col, p->brp);
   WG_LAUNCH_CHECK();
@@ -1162,7 +1162,7 @@ int get_lds1_plan(wg_laplacian_s* L, bool active_only, Lds1Plan** out) {
     return WG_OK;
   }
   if ((rc = dmalloc(&p->bcol, (size_t)nnz + 8))) return bail(rc);
-  WG_HIP_TRY(hipMemset(p->bcol, 0, sizeof(uint16_t) * ((size_t)nnz + 8)));
+  WG_HIP_TRY(dzero(p->bcol, sizeof(uint16_t) * ((size_t)nnz + 8)));
   {
     int64_t run = 0;
     for (int64_t i = 0; i < ncnt; ++i) {

@@ -624,7 +624,7 @@ int get_plan(wg_laplacian_s* L, int LF, int VEC, bool active_only, Plan** out, b
     if (!rc) rc = upload(&p.rowchunks, sp.rowchunks);
     if (!rc) rc = dmalloc(&p.partial, sp.chunks.size() * (size_t)p.width);
     if (!rc) rc = dmalloc(&p.arrivals, sp.rowchunks.size());
-    if (!rc && hipMemset(p.arrivals, 0, sizeof(uint32_t) * sp.rowchunks.size()) != hipSuccess) rc = WG_ERR_HIP;
+    if (!rc && dzero(p.arrivals, sizeof(uint32_t) * sp.rowchunks.size()) != hipSuccess) rc = WG_ERR_HIP;
   }
   if (rc) {
     p.release();

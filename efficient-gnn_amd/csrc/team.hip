@@ -101,7 +101,7 @@ int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32
   if (!rc) rc = upload(&tp->sell, w.sell);
   if (!rc) rc = dmalloc(&tp->wpart, (size_t)std::max(w.n_slots, 1) * tp->width);
   if (!rc) rc = dmalloc(&tp->warr, (size_t)std::max(w.n_long, 1));
-  if (!rc && hipMemset(tp->warr, 0, sizeof(uint32_t) * std::max(w.n_long, 1)) != hipSuccess)
+  if (!rc && dzero(tp->warr, sizeof(uint32_t) * std::max(w.n_long, 1)) != hipSuccess)
     rc = fail(WG_ERR_HIP, "team waves: upload failed");
   if (rc) tp->release();  // no half-built table (wd non-null marks a built one)
   return rc;

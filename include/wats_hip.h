@@ -10,6 +10,11 @@
  *   - Every pointer argument is a DEVICE pointer (hipMalloc / torch CUDA tensor
  *     storage) unless its name ends in `_host`.  Buffers are caller-owned,
  *     row-major, contiguous, F (signal columns) innermost.
+ *   - Alignment: a float buffer needs 4-byte alignment only (int32 / int64 / double buffers
+ *     that of their element).  Buffers aligned to 16 bytes take the vector kernels (and, in
+ *     wg_wavelet_features, the fused finalize and the folded first launch); any other base runs
+ *     the 8-byte or scalar forms of the same kernels: same values to the parity tolerance, not
+ *     necessarily the same bits as the aligned call.  No entry point rejects a misaligned buffer.
  *   - `stream` is a hipStream_t passed as void* (NULL = legacy default stream).
  *     All work is enqueued on it; no entry point synchronises the device
  *     except the ones documented as "synchronous" (graph creation / dense

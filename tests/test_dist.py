@@ -472,7 +472,7 @@ def test_ipc_chain_with_an_empty_shard(F, exchange):
     assert_parity(np.concatenate([r[1] for r in res]), ref["S"], what=f"empty shard F={F}")
 
 
-def _width_worker(rank, world, port, widths, q):
+def _width_worker(rank, world, port, widths, q, knobs=None, poison=None):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     import sys
@@ -485,10 +485,14 @@ def _width_worker(rank, world, port, widths, q):
         r0, r1 = int(bounds[rank]), int(bounds[rank + 1])
         lo, hi = g.indptr[r0], g.indptr[r1]
         sw = ShardedWavelet(g.indptr[r0:r1 + 1] - lo, g.indices[lo:hi], None, g.n, bounds, exchange="ipc",
-                            device="cuda:0", max_features=max(widths))
-        sw.L.tune(tiles=1, tile_th=8, tile_max=3)
+                            device="cuda:0", max_features=max(list(widths) + list(poison or [])))
+        sw.L.tune(tiles=1, tile_th=8, tile_max=3, **(knobs or {}))
         out = []
-        for F in widths:
+        for i, F in enumerate(widths):
+            if poison:   # an all-NaN signal of width poison[i] on every rank: NaN in every halo column that width pulls
+                Hn, Sn = sw.wavelet_features(torch.full((r1 - r0, poison[i]), float("nan")), k=6, s=0.8)
+                torch.cuda.synchronize()
+                assert bool(torch.isnan(Sn).all())
             X = np.random.default_rng(F).standard_normal((g.n, F)).astype(np.float32)
             H, S = sw.wavelet_features(torch.from_numpy(X[r0:r1]), k=6, s=0.8)
             torch.cuda.synchronize()
@@ -536,3 +540,45 @@ def test_ipc_chain_width_changes():
         X = np.random.default_rng(F).standard_normal((g.n, F)).astype(np.float32)
         ref = O.graph_wavelet_features(g.to_scipy(), k=6, s=0.8, X0=X, return_all=True)
         assert_parity(np.concatenate([r[1][i] for r in res]), ref["S"], what=f"IPC width change F={F} (call {i})")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("widths,poison,knobs", [([45, 41, 44, 41], [48, 48, 48, 48], {}),
+                                                 ([41, 37, 41], [44, 44, 44], {"fpad": 16})], ids=["auto-pad", "fpad16"])
+def test_ipc_chain_narrower_pulls_after_nan_calls(widths, poison, knobs):
+    """The pull moves the signal's columns rounded up to 4 of the exchanged width and leaves the rest of a
+    halo row alone.  Before every checked width an all-NaN signal of a WIDER width at the same exchanged
+    width (48) runs on every rank, so every halo column the checked call does not pull again holds NaN.
+    fpad16: the NaN F = 44 call pulls 44 columns, the checked F = 37 pulls 40 and nothing re-zeroes
+    (pads_zeroed stays 48), so halo columns 40 .. 43 are stale NaN during the checked chain; the
+    checked F = 41 pulls 44 again.  auto-pad: a NaN F = 48 call pulls the full width (pads_zeroed = 0), the
+    checked F = 45 pulls all of it again, and F = 41 / 44 pull 44, which must re-zero columns 44 .. 47 first;
+    at the automatic padding the pulled width is the exchanged width or 4 less, so no narrower pull can follow
+    a wider one without that re-zero.  A step is column-wise, so a stale halo column c can reach column c of the
+    own rows only, c >= F, which no finalize reads: every result matches the oracle (and is finite)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_width_worker, args=(r, 2, port, widths, q, knobs, poison)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = []
+    try:
+        for _ in range(2):
+            res.append(q.get(timeout=170))
+            if isinstance(res[-1][1], str):
+                pytest.fail(f"rank {res[-1][0]}: {res[-1][1]}")
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+    res.sort(key=lambda t: t[0])
+    g = rmat_graph(4000, 120000, seed=9)
+    for i, F in enumerate(widths):
+        X = np.random.default_rng(F).standard_normal((g.n, F)).astype(np.float32)
+        ref = O.graph_wavelet_features(g.to_scipy(), k=6, s=0.8, X0=X, return_all=True)
+        S = np.concatenate([r[1][i] for r in res])
+        assert_parity(S, ref["S"], what=f"IPC narrower pull F={F} (call {i}, {knobs})")
