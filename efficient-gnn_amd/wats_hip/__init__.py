@@ -14,7 +14,9 @@ propagation as a HIP SpMM), EdgeProbe / target_flip_scores / toggle_edges
 (its gradient at edge positions and the attack's flip, HIP SDDMM),
 RowNormalizedAdjacency.with_flips / FlippedAdjacency (a flipped graph as a view
 of its parent's operators, committed to CSR without a rebuild), edge_index_to_csr / DeviceCSR (edge_index to canonical CSR on the device), metrics
-(device ECE).
+(device ECE), GATSCalibrator / GATS / CalibAttentionLayer / shortest_path_length (the
+comparison calibrator of the harness: its edge softmax, both aggregations and its BFS in HIP,
+edge_softmax_attention on an AttentionGraph).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -44,5 +46,15 @@ from .gcn import (  # noqa: F401
 from .head import wats_head  # noqa: F401
 from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
 from .flips import FlippedAdjacency  # noqa: F401
+from .gats import (  # noqa: F401
+    GATS,
+    AttentionGraph,
+    CalibAttentionLayer,
+    GATSCalibrator,
+    calibrate_with_gats,
+    csr_transpose_map,
+    edge_softmax_attention,
+    shortest_path_length,
+)
 
 __version__ = "0.1.0"

@@ -95,6 +95,13 @@ SIGNATURES = {
     "wg_wats_head_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 8 + [c_vp]),
     "wg_wats_head_workspace": (ctypes.c_int, [c_i64, c_i64, c_i32, ctypes.POINTER(c_i64)]),
     "wg_wats_head_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 15 + [c_vp]),
+    "wg_csr_transpose_map": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wg_bfs_levels": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "wg_gat_long_row": (ctypes.c_int, []),
+    "wg_gat_forward": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wg_gat_backward": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                       c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "wg_dist_unique_id": (ctypes.c_int, [c_vp]),
     "wg_dist_create": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "wg_dist_destroy": (ctypes.c_int, [c_vp]),

@@ -527,6 +527,77 @@ int wg_wats_head_backward(int64_t n, int64_t F, int64_t C, int32_t hid, const fl
                           const float* grad_out, float* grad_logits, float* gW1, float* gb1,
                           float* gW2, float* gb2, void* workspace, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the attention layer of the GATS calibrator (reference
+ * calibration/GATS.py), the calibrator the harness runs next to WATS
+ * (benchmark_calibration_methods.py:317-354).
+ *
+ * wg_csr_transpose_map: the transposed structure of a canonical CSR (square,
+ * n x n, columns ascending in each row): t_indptr int64 [n + 1], t_indices int32
+ * [nnz] ascending in each row, and t_pos int32 [nnz], the position in `indices`
+ * of the entry that transposed entry e' mirrors.  The layer aggregates over the
+ * targets of edge_index = dense_to_sparse(adj) (GATS.py:199, :134-139: row i of
+ * the by-destination CSR is column i of adj), and its backward also runs over
+ * the sources.  nnz == indptr[n].  Synchronous, temporary memory inside the call.
+ *
+ * wg_bfs_levels: shortest_path_length (GATS.py:25-49) on the device.  indptr /
+ * indices list each node's out-neighbours (the targets of its edges); mask is
+ * uint8 [n]; dist int64 [n] gets the level of every node reached at a level in
+ * [0, max_hop) and INT64_MAX elsewhere: as in the reference only levels
+ * 0 .. max_hop - 1 are ever assigned (bfs_depth = 2: the values are 0, 1 and the
+ * maximum), and max_hop == 0 assigns none.  Self loops never change a level.
+ * One launch per level; integer stores only, every writer of a cell writes the
+ * same value.  Asynchronous, no allocation.
+ *
+ * wg_gat_forward: CalibAttentionLayer.message / aggregation (GATS.py:134-167).
+ * indptr / indices: the CSR by destination -- row i lists In(i), the sources j of
+ * the edges j -> i, with the self loop of GATS.py:102-106 already in it.  With
+ * a (n, C), t (n, Hh), conf (n), row-major float32:
+ *   d_ij = sum_c a_i[c] a_j[c];   e_ij = d_ij > 0 ? d_ij : negative_slope * d_ij
+ *   p_ij = exp(e_ij - max_l e_il) / sum_l exp(e_il - max_l e_il)     over l in In(i)
+ *   sim[i, h] = sum_j p_ij t[j, h];   dconf[i] = sum_j (conf[i] - conf[j])
+ * (a row without entries gives 0).  e_save [nnz], row_max [n], row_den [n]
+ * (float64: e_ij, the row's maximum and its denominator) are what the backward
+ * needs; all three NULL for inference.
+ *
+ * wg_gat_backward: from g_sim = d loss / d sim (n, Hh), with q_ij = g_i . t_j,
+ * m_i = sum_j p_ij q_ij, r_ij = p_ij (q_ij - m_i), s_ij = r_ij * (d_ij > 0 ? 1 :
+ * negative_slope) (the slope at d_ij == 0, as torch's leaky_relu backward):
+ *   grad_t[j, h] = sum_{i : j in In(i)} p_ij g_sim[i, h]
+ *   grad_a[i, c] = sum_{j in In(i)} s_ij a[j, c] + sum_{l : i in In(l)} s_li a[l, c]
+ * overwritten, not accumulated; dconf carries no gradient.  edge_work: 2 nnz
+ * float64 of scratch (p and s per entry).  t_indptr / t_indices / t_pos: the
+ * transpose map of indptr / indices.
+ *
+ * Rows of at least wg_gat_long_row() entries (256) are run by a workgroup each
+ * and must be listed by the caller, ascending: long_rows [n_long] = the rows i
+ * with indptr[i + 1] - indptr[i] >= wg_gat_long_row(); t_long_rows [n_tlong] =
+ * the nodes for which that holds in indptr or in t_indptr.  A listed row that is
+ * not long is harmless; a long row that is not listed is not computed.
+ * 1 <= C; 1 <= Hh <= 64.  All sums, products and exp in float64, in an order
+ * fixed by the rows and nnz / n; no float atomics: the same input gives the same
+ * bits.  Column ids and positions are checked on the device in the
+ * bounds-checked variant only; every other argument before any device call.
+ * Forward and backward are asynchronous, allocate nothing and may be captured;
+ * n == 0 is WG_OK with no launch.
+ * ---------------------------------------------------------------------- */
+int wg_csr_transpose_map(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                         int64_t* t_indptr, int32_t* t_indices, int32_t* t_pos, void* stream);
+int wg_bfs_levels(int64_t n, const int64_t* indptr, const int32_t* indices, const uint8_t* mask,
+                  int32_t max_hop, int64_t* dist, void* stream);
+int wg_gat_long_row(void);
+int wg_gat_forward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                   int64_t n_long, const int32_t* long_rows, int64_t C, int64_t Hh, const float* a,
+                   const float* t, const float* conf, double negative_slope, float* sim,
+                   float* dconf, double* e_save, double* row_max, double* row_den, void* stream);
+int wg_gat_backward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                    int64_t n_long, const int32_t* long_rows, const int64_t* t_indptr,
+                    const int32_t* t_indices, const int32_t* t_pos, int64_t n_tlong,
+                    const int32_t* t_long_rows, int64_t C, int64_t Hh, const float* a,
+                    const float* t, const double* e_save, const double* row_max,
+                    const double* row_den, const float* g_sim, double negative_slope,
+                    float* grad_a, float* grad_t, double* edge_work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
