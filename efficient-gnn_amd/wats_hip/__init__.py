@@ -16,7 +16,8 @@ RowNormalizedAdjacency.with_flips / FlippedAdjacency (a flipped graph as a view
 of its parent's operators, committed to CSR without a rebuild), edge_index_to_csr / DeviceCSR (edge_index to canonical CSR on the device), metrics
 (device ECE), GATSCalibrator / GATS / CalibAttentionLayer / shortest_path_length (the
 comparison calibrator of the harness: its edge softmax, both aggregations and its BFS in HIP,
-edge_softmax_attention on an AttentionGraph).
+edge_softmax_attention on an AttentionGraph), CaGCN / GCNConv / calibration_loss (the GCN-based calibrator: PyG's
+gcn_norm + propagate as one HIP aggregation, sym_norm_aggregate on a SymNormGraph).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -55,6 +56,13 @@ from .gats import (  # noqa: F401
     csr_transpose_map,
     edge_softmax_attention,
     shortest_path_length,
+)
+from .cagcn import (  # noqa: F401
+    CaGCN,
+    GCNConv,
+    SymNormGraph,
+    calibration_loss,
+    sym_norm_aggregate,
 )
 
 __version__ = "0.1.0"

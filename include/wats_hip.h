@@ -598,6 +598,46 @@ int wg_gat_backward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t
                     const double* row_den, const float* g_sim, double negative_slope,
                     float* grad_a, float* grad_t, double* edge_work, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the aggregation of the CaGCN calibrator (reference
+ * calibration/CaGCN.py:104-108).  Its scaling model is two PyG GCNConv layers
+ * on edge_index = dense_to_sparse(adj); GCNConv calls gcn_norm
+ * (add_remaining_self_loops, deg = the in-degree with the loop, one weight
+ * deg_i^-1/2 deg_j^-1/2 per edge) and propagates the scaled source rows with
+ * aggr='add'.  wg_symnorm_aggregate replaces gcn_norm and that propagation:
+ *
+ *   out[i][c] = act( dinv[i] * sum_{p in [indptr[i], indptr[i+1])}
+ *                                  dinv[indices[p]] * x[indices[p]][c]  +  bias[c] )
+ *
+ * indptr / indices: the canonical CSR by destination (row i lists the sources
+ * of the edges into i, ascending, no duplicates) with one self loop per node
+ * already in it; dinv float32 [n] = in-degree^-1/2; x and out row-major (n, C)
+ * float32, out must not alias x; bias C floats or NULL; relu != 0: act is
+ * v < 0 ? 0 : v (a NaN stays), else the identity.  No edge values are read.
+ * The gradient w.r.t. x is the same call on the transposed structure
+ * (wg_csr_transpose_map) with bias NULL and relu 0:
+ *   grad_x[j] = dinv[j] * sum_{i : j in row i} dinv[i] * g[i].
+ *
+ * Rows of at least wg_symnorm_long_row() entries (128) are run by a workgroup
+ * each, from long_rows [n_long] (ascending).  A listed row that is not long is
+ * harmless, and a long row that is not listed is still computed (by one
+ * sub-group of lanes: slowly).  Products and sums in float64, the epilogue
+ * dinv_i * acc + bias_c in float64 rounded once to float32; the order of a
+ * row's sum is fixed by the row, C and the launch shape; no float atomics: the
+ * same input gives the same bits.  Any C >= 1; 16-byte loads when C % 4 == 0
+ * and x / out are 16-byte aligned, dword loads otherwise.  Column ids, row
+ * ranges and listed rows are checked on the device in the bounds-checked
+ * variant only; every other argument before any device call: n == 0 or C == 0
+ * is WG_OK with no launch; a negative size, a NULL indptr / dinv / x / out
+ * (indices with nnz > 0, long_rows with n_long > 0) or out == x is
+ * WG_ERR_INVALID.  Asynchronous, allocates nothing, may be captured.
+ * ---------------------------------------------------------------------- */
+int wg_symnorm_long_row(void);
+int wg_symnorm_aggregate(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                         int64_t n_long, const int32_t* long_rows, const float* dinv, int64_t C,
+                         const float* x, const float* bias, int32_t relu, float* out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
