@@ -17,7 +17,9 @@ of its parent's operators, committed to CSR without a rebuild), edge_index_to_cs
 (device ECE), GATSCalibrator / GATS / CalibAttentionLayer / shortest_path_length (the
 comparison calibrator of the harness: its edge softmax, both aggregations and its BFS in HIP,
 edge_softmax_attention on an AttentionGraph), CaGCN / GCNConv / calibration_loss (the GCN-based calibrator: PyG's
-gcn_norm + propagate as one HIP aggregation, sym_norm_aggregate on a SymNormGraph).
+gcn_norm + propagate as one HIP aggregation, sym_norm_aggregate on a SymNormGraph), SimCalib / SimilarityBank /
+similarity_temperature (the similarity-based calibrator: cosine similarity, softmax and the confidence product as one
+fused HIP pass per direction, no (N, N_val) matrix).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -63,6 +65,12 @@ from .cagcn import (  # noqa: F401
     SymNormGraph,
     calibration_loss,
     sym_norm_aggregate,
+)
+from .simcalib import (  # noqa: F401
+    SimCalib,
+    SimilarityBank,
+    raw_similarity_temperature,
+    similarity_temperature,
 )
 
 __version__ = "0.1.0"

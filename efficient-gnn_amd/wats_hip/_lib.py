@@ -105,6 +105,9 @@ SIGNATURES = {
     "wg_symnorm_long_row": (ctypes.c_int, []),
     "wg_symnorm_aggregate": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
                                             c_vp]),
+    "wg_simcalib_max_d": (ctypes.c_int, []),
+    "wg_simcalib_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
+    "wg_simcalib_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
     "wg_dist_unique_id": (ctypes.c_int, [c_vp]),
     "wg_dist_create": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "wg_dist_destroy": (ctypes.c_int, [c_vp]),

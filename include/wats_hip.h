@@ -638,6 +638,52 @@ int wg_symnorm_aggregate(int64_t n, int64_t nnz, const int64_t* indptr, const in
                          const float* x, const float* bias, int32_t relu, float* out,
                          void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the similarity temperature of the SimCalib calibrator
+ * (reference calibration/SimCalib.py:49-58, 91-105).  The reference builds the
+ * (N, N_val) cosine matrix of the latent rows against the validation bank, its
+ * softmax(. / tau) and the product with 1 / (confidence + eps), and autograd
+ * keeps all of them.  These two entries compute the same without any (n, m)
+ * buffer.  x (n, d) float32 latent rows, unnormalised; bank (m, d) float32,
+ * already L2-normalised; inv_conf (m) float32; all row-major.
+ *
+ *   a_i = x_i / max(|x_i|, 1e-12)          s_ij = a_i . b_j
+ *   w_ij = softmax_j(s_ij / tau)           t_i = sum_j w_ij inv_conf_j
+ *
+ * wg_simcalib_forward writes t (n), unclamped, and stats (n, 3) float64: each
+ * row's maximum of s_ij / tau, the softmax denominator relative to it and t_i
+ * before its rounding to float32, which the backward needs (with them its
+ * weights sum to one against the same t_i as the forward's, to rounding of
+ * single terms).  wg_simcalib_backward takes g = dL/dt (n; the caller has
+ * applied the clamp's mask) with the forward's stats and writes
+ * gx (n, d) = dL/dx:  ga_i = (g_i / tau) sum_j w_ij (inv_conf_j - t_i) b_j,
+ * then F.normalize's Jacobian as torch differentiates it,
+ * gx_i = (ga_i - a_i (a_i . ga_i)) / |x_i| for |x_i| >= 1e-12, else
+ * ga_i / 1e-12.  There is no gradient w.r.t. bank or inv_conf (the reference
+ * detaches both).
+ *
+ * Both products run on v_mfma_f32_32x32x2_f32 (float32 in, float32 k-ordered
+ * fma chains); exp is float32, numerator and denominator are float64 sums
+ * with a running maximum, right for any tau > 0; the row norm is a float64
+ * sum rounded once.
+ * Every sum has a fixed order, bank rows are never split over workgroups and
+ * no float atomics are used: the same input gives the same bits.  A NaN in
+ * row i of x reaches t_i and gx_i only.
+ *
+ * Any n >= 1, m >= 1 and 1 <= d <= wg_simcalib_max_d() (256: a row tile and
+ * its d-wide gradient live in registers).  Checked before any device call:
+ * n, m or d <= 0, a NULL pointer, tau <= 0, non-finite or so small that
+ * 1 / tau overflows float32, gx == x: WG_ERR_INVALID; d above the limit or
+ * n / m above int32: WG_ERR_UNSUPPORTED.  Asynchronous, allocates nothing, may
+ * be captured.
+ * ---------------------------------------------------------------------- */
+int wg_simcalib_max_d(void);
+int wg_simcalib_forward(int64_t n, int64_t m, int64_t d, const float* x, const float* bank,
+                        const float* inv_conf, double tau, float* t, double* stats, void* stream);
+int wg_simcalib_backward(int64_t n, int64_t m, int64_t d, const float* x, const float* bank,
+                         const float* inv_conf, double tau, const double* stats, const float* g,
+                         float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
