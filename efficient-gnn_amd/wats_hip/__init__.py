@@ -19,7 +19,9 @@ comparison calibrator of the harness: its edge softmax, both aggregations and it
 edge_softmax_attention on an AttentionGraph), CaGCN / GCNConv / calibration_loss (the GCN-based calibrator: PyG's
 gcn_norm + propagate as one HIP aggregation, sym_norm_aggregate on a SymNormGraph), SimCalib / SimilarityBank /
 similarity_temperature (the similarity-based calibrator: cosine similarity, softmax and the confidence product as one
-fused HIP pass per direction, no (N, N_val) matrix).
+fused HIP pass per direction, no (N, N_val) matrix), DCGC / DecisiveEdge / EdgeWeightGraph / edge_mlp_weights /
+weighted_propagate / homophily_weights (the edge-weight calibrator: its edge MLP as one fused pass per direction on the
+float32 matrix cores with no (E, k) tensor, and the base model's propagation with the edge values as an argument).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -71,6 +73,14 @@ from .simcalib import (  # noqa: F401
     SimilarityBank,
     raw_similarity_temperature,
     similarity_temperature,
+)
+from .dcgc import (  # noqa: F401
+    DCGC,
+    DecisiveEdge,
+    EdgeWeightGraph,
+    edge_mlp_weights,
+    homophily_weights,
+    weighted_propagate,
 )
 
 __version__ = "0.1.0"

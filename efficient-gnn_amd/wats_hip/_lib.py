@@ -108,6 +108,17 @@ SIGNATURES = {
     "wg_simcalib_max_d": (ctypes.c_int, []),
     "wg_simcalib_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "wg_simcalib_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),
+    "wg_edge_mlp_max_c": (ctypes.c_int, []),
+    "wg_edge_mlp_tile": (ctypes.c_int, []),
+    "wg_edge_mlp_workspace": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_edge_mlp_forward": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_f64, ctypes.c_uint64,
+                                                                                          c_vp, c_vp, c_vp]),
+    "wg_edge_mlp_backward": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_f64, ctypes.c_uint64]
+                             + [c_vp] * 13),
+    "wg_edge_aggregate_long_row": (ctypes.c_int, []),
+    "wg_edge_aggregate": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                         c_vp, c_vp]),
+    "wg_edge_pair_inv_distance": (ctypes.c_int, [c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_f64, c_vp, c_vp]),
     "wg_dist_unique_id": (ctypes.c_int, [c_vp]),
     "wg_dist_create": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "wg_dist_destroy": (ctypes.c_int, [c_vp]),

@@ -684,6 +684,109 @@ int wg_simcalib_backward(int64_t n, int64_t m, int64_t d, const float* x, const 
                          const float* inv_conf, double tau, const double* stats, const float* g,
                          float* gx, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the DCGC calibrator (reference calibration/DCGC.py).
+ * Decisive_Edge.get_weight (DCGC.py:66-79) gives every stored entry (r, c) of
+ * the adjacency, in the row-major order of dense_to_sparse (= the canonical CSR
+ * by row; e numbers its entries), the weight
+ *
+ *   z1 = W1 [emb_r ; emb_c] + b1   h1 = D1 * relu(z1)     (4C units)
+ *   z2 = W2 h1 + b2                h2 = D2 * relu(z2)     (2C units)
+ *   z3 = w3 . h2 + b3              w_e = relu(z3)
+ *
+ * (DCGC.py:36-44, :70-73: `col, row = edge_index` swaps the names, f1 = emb[r],
+ * f2 = emb[c], the weight lands at [r, c]; the adjacency's own values are not
+ * read).  emb (n, C) float32; W1 (4C, 2C), b1 (4C), W2 (2C, 4C), b2 (2C),
+ * w3 (2C), b3 (1): torch Linear layouts, float32.  The reference builds the
+ * (E, 2C), (E, 4C) and (E, 2C) tensors and autograd keeps them; these entries
+ * keep an entry's activations in registers and the backward recomputes them:
+ * no buffer of nnz x k floats with k > 4 exists.  The three products run on
+ * v_mfma_f32_32x32x2_f32 (float32 in, float32 k-ordered fma chains); the last
+ * layer is a float64 sum per entry.
+ *
+ * Dropout (D1, D2; DCGC.py:39, :42).  p == 0: all ones, nothing is hashed.
+ * Else unit j (0-based) of layer l (1 or 2) of entry e (its CSR position) is
+ * kept iff, in unsigned 64-bit arithmetic modulo 2^64,
+ *   x  = (seed ^ (0x9E3779B97F4A7C15 * l)) + e * 0xBF58476D1CE4E5B9
+ *                                           + j * 0x94D049BB133111EB
+ *   x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;
+ *   x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *   (uint32)(x >> 32) >= (uint32) floor(p * 2^32)
+ * and a kept unit is scaled by (float)(1 / (1 - p)).  Examples with seed = 7,
+ * l = 1: (e, j) = (0, 0), (1, 0), (0, 1), (123456, 77) give the 32-bit words
+ * 0xf75f04cb, 0x73086d4d, 0x5f2f8c48, 0xc768449f; with l = 2: 0xb3466f8a,
+ * 0xfe2295de, 0x14959e27, 0x3b9c8399.  The stream is NOT torch's: a run with
+ * p > 0 does not reproduce the reference's masks, only their distribution.
+ *
+ * wg_edge_mlp_forward writes w (nnz).  wg_edge_mlp_backward takes g_w = dL/dw
+ * (nnz) and the forward's inputs and overwrites the six parameter gradients
+ * (the parameters' shapes) and, unless g_emb is NULL, g_emb (n, C) = dL/demb;
+ * g_emb needs the transposed CSR with its entry map (wg_csr_transpose_map);
+ * with g_emb NULL those three may be NULL.  workspace: wg_edge_mlp_workspace
+ * bytes, 16-byte aligned, scratch (nothing is kept between calls).  It grows
+ * with n C, with 256 x the parameter count and with at most 9 bytes per entry.
+ *
+ * Order.  The backward walks the entries in tiles of wg_edge_mlp_tile() (1024),
+ * tile t on workgroup t mod min(tiles, 256), 128 entries at a time.  The weight
+ * gradients are float32 MFMA chains over those 128 entries in ascending order;
+ * everything across them, and so across tiles, is added in float64 in ascending
+ * order, then the workgroups' sums in ascending order.  Bias gradients are
+ * float64 sums; a layer's products are float32 chains of 32 terms met in
+ * float64.  g_emb is a float64 sum per node over its
+ * entries in ascending CSR position (the emb_r half) and ascending transposed
+ * position (the emb_c half, a second recomputing pass).  No float atomics: the
+ * same input gives the same bits.  A NaN in row i of emb reaches only the
+ * weights of the entries in row i or column i.
+ *
+ * 1 <= C <= wg_edge_mlp_max_c() (48).  Checked before any device call: a
+ * negative n / nnz, C <= 0, p outside [0, 1), a NULL pointer that is needed,
+ * g_emb == emb: WG_ERR_INVALID; C above the limit, n or nnz above int32:
+ * WG_ERR_UNSUPPORTED.  n == 0 or nnz == 0 is WG_OK: the forward writes
+ * nothing, the backward writes zero gradients.  Row and column ids and the map
+ * are checked on the device in the bounds-checked variant only.  Asynchronous,
+ * allocate nothing, may be captured.
+ *
+ * wg_edge_aggregate: the base model's propagation (src/gnn/model.py:43-52) on
+ * an adjacency whose values are an argument:
+ *   out[i] = row_scale[i] * sum_{p in [indptr[i], indptr[i+1])}
+ *            val[map ? map[p] : p] * col_scale[indices[p]] * x[indices[p]]
+ * (either scale NULL = 1).  Forward: row_scale = 1 / deg, deg_i = sum_c w_ic
+ * with 0 -> 1 (model.py:43-45).  Gradient w.r.t. x: the transposed structure,
+ * map = the transpose map, col_scale = 1 / deg.  The gradient w.r.t. a value
+ * is (g_r . x_c - g_r . y_r) / deg_r (wg_sddmm + wg_rowdot).  Rows of at least
+ * wg_edge_aggregate_long_row() entries (128) are run by a workgroup each from
+ * long_rows (ascending; a long row that is not listed is still computed, a
+ * listed short row is harmless).  Products and sums in float64 in a fixed
+ * order, rounded once; 16-byte loads when C % 4 == 0 and x / out are 16-byte
+ * aligned.  out must not alias x.  n == 0 or C == 0: WG_OK, no launch.
+ *
+ * wg_edge_pair_inv_distance: DCGC.get_homo_weight's coefficient
+ * (DCGC.py:164-165): out[e] = 1 / (sqrt(sum_k (Q[rows[e]][k] - Q[cols[e]][k])^2)
+ * + alpha), the sum in float64 over the differences themselves (rows[e] ==
+ * cols[e] gives exactly (float)(1 / alpha)).  Q (n, C) float32.
+ * ---------------------------------------------------------------------- */
+int wg_edge_mlp_max_c(void);
+int wg_edge_mlp_tile(void);
+int wg_edge_mlp_workspace(int64_t n, int64_t nnz, int64_t C, int64_t* bytes);
+int wg_edge_mlp_forward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                        int64_t C, const float* emb, const float* W1, const float* b1,
+                        const float* W2, const float* b2, const float* w3, const float* b3,
+                        double p, uint64_t seed, void* workspace, float* w, void* stream);
+int wg_edge_mlp_backward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                         int64_t C, const float* emb, const float* W1, const float* b1,
+                         const float* W2, const float* b2, const float* w3, const float* b3,
+                         double p, uint64_t seed, const float* g_w, const int64_t* t_indptr,
+                         const int32_t* t_indices, const int32_t* t_pos, float* gW1, float* gb1,
+                         float* gW2, float* gb2, float* gw3, float* gb3, float* g_emb,
+                         void* workspace, void* stream);
+int wg_edge_aggregate_long_row(void);
+int wg_edge_aggregate(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                      int64_t n_long, const int32_t* long_rows, const float* val,
+                      const int32_t* map, const float* row_scale, const float* col_scale, int64_t C,
+                      const float* x, float* out, void* stream);
+int wg_edge_pair_inv_distance(int64_t nnz, const int32_t* rows, const int32_t* cols, int64_t C,
+                              int64_t n, const float* Q, double alpha, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
