@@ -313,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(int64_t n, int64_t F, 
     load_vec<VEC>((closed ? X0int : Sint) + row * ldi + fs * VEC, x);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      s[j] = closed ? coef * (double)x[j] : (double)x[j];
+      s[j] = closed ? stored(coef * (double)x[j]) : (double)x[j];
       part += fabs(s[j]);
     }
   }
@@ -344,11 +344,11 @@ __global__ __launch_bounds__(kBlock) void finalize_wide_kernel(int64_t n, int64_
   const float* src = closed ? X0int : Sint;
   const double c = closed ? coef : 1.0;
   double part = 0.0;
-  for (int64_t f = lane; f < F; f += 64) part += fabs(c * (double)src[row * ldi + f]);
+  for (int64_t f = lane; f < F; f += 64) part += fabs(stored(c * (double)src[row * ldi + f]));
   for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off, 64);
   const double den = part + 1e-8;
   for (int64_t f = lane; f < F; f += 64) {
-    const double s = c * (double)src[row * ldi + f];
+    const double s = stored(c * (double)src[row * ldi + f]);
     if (S) S[r * F + f] = (float)s;
     if (H) H[r * F + f] = (float)(s / den);
   }
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(kBlock) void permute_in_closed_kernel(int64_t n, in
     if (active) {
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        sv[j] = closed ? coef * (double)x[g][j] : (double)x[g][j];
+        sv[j] = closed ? stored(coef * (double)x[g][j]) : (double)x[g][j];
         part += fabs(sv[j]);
       }
       if (!closed) {

@@ -110,6 +110,11 @@ __device__ __forceinline__ void load_vec(const float* p, float (&x)[VEC]) {
   }
 }
 
+// A float64 result as the caller reads it back from its float32 store.  H is the normalisation of the S
+// that is RETURNED (H = fl32(S / (|S|_1 + 1e-8)) for the float32 S, as wg_row_l1_normalize of it and the
+// separate finalize compute it), not of the unrounded sums behind it.
+__device__ __forceinline__ double stored(double x) { return (double)(float)x; }
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -282,13 +287,13 @@ __device__ __forceinline__ void step_epilogue(const StepArgs& a, int64_t row, in
     if (a.H) {
       double part = 0.0;
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) part += fabs(s[j]);
+      for (int j = 0; j < VEC; ++j) part += fabs(stored(s[j]));
       double tot = 0.0;
       for (int q = 0; q < a.LF; ++q) tot += __shfl(part, lane0 + q, 64);
       const double den = tot + 1e-8;
       double h[VEC];
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) h[j] = s[j] / den;
+      for (int j = 0; j < VEC; ++j) h[j] = stored(s[j]) / den;
       store_vec<VEC>(a.H + oo, h);
     }
   }

@@ -71,7 +71,7 @@ __device__ __forceinline__ void closed_wave(const TeamArgs& t, int64_t cw) {
     double part = 0.0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      sv[j] = t.coef * (double)x[q][j];
+      sv[j] = stored(t.coef * (double)x[q][j]);
       part += fabs(sv[j]);
     }
     double tot = 0.0;  // the row's L1 norm, in column order (finalize_kernel's order)
@@ -273,13 +273,13 @@ __device__ __forceinline__ void epilogue_spec(const StepArgs& a, int row, int fs
     store_vec<4>(a.S_out + oo, t);
     double part = 0.0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) part += fabs(t[j]);
+    for (int j = 0; j < 4; ++j) part += fabs(stored(t[j]));
     double tot = 0.0;
     for (int q = 0; q < a.LF; ++q) tot += __shfl(part, lane0 + q, 64);
     const double den = tot + 1e-8;
     double h[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = t[j] / den;
+    for (int j = 0; j < 4; ++j) h[j] = stored(t[j]) / den;
     store_vec<4>(a.H + oo, h);
   }
 }

@@ -160,7 +160,8 @@ int wg_log1p_degree(wg_laplacian_t L, float* x0, void* stream);
  * heat-kernel sum of calibration/WATS.py:65-68 is fused:
  *   k == 1:  S = alpha0 * T_0 + alpha_k * T_1;    k >= 2:  S += alpha_k * T_k.
  * If H != NULL (last step) the row-L1 normalisation of WATS.py:71-72 is fused:
- *   H = S / (sum_f |S| + 1e-8).  Row sums accumulate in float64.
+ *   H = S / (sum_f |S| + 1e-8) of the float32 S this call stores (as wg_row_l1_normalize of it, and as
+ *   every H that wg_wavelet_features returns): a float64 quotient rounded once.  Row sums accumulate in float64.
  * ---------------------------------------------------------------------- */
 int wg_cheb_step(wg_laplacian_t L, int32_t k, int64_t F, const float* t_km1,
                  const float* t_km2, float* t_k, float* S, float* H,
