@@ -21,7 +21,10 @@ gcn_norm + propagate as one HIP aggregation, sym_norm_aggregate on a SymNormGrap
 similarity_temperature (the similarity-based calibrator: cosine similarity, softmax and the confidence product as one
 fused HIP pass per direction, no (N, N_val) matrix), DCGC / DecisiveEdge / EdgeWeightGraph / edge_mlp_weights /
 weighted_propagate / homophily_weights (the edge-weight calibrator: its edge MLP as one fused pass per direction on the
-float32 matrix cores with no (E, k) tensor, and the base model's propagation with the edge values as an argument).
+float32 matrix cores with no (E, k) tensor, and the base model's propagation with the edge values as an argument),
+GETSCalibrator / GCNExpert / gated_sym_norm_head / calibrate_with_gets (the mixture-of-graph-experts calibrator: the
+last propagation of every expert, the top-k gated mixture, softplus and log_softmax as one HIP pass that reads only
+the selected slices, no (N, E, C) tensor of aggregated outputs).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -81,6 +84,12 @@ from .dcgc import (  # noqa: F401
     edge_mlp_weights,
     homophily_weights,
     weighted_propagate,
+)
+from .gets import (  # noqa: F401
+    GCNExpert,
+    GETSCalibrator,
+    calibrate_with_gets,
+    gated_sym_norm_head,
 )
 
 __version__ = "0.1.0"

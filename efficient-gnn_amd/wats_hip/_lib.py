@@ -105,6 +105,12 @@ SIGNATURES = {
     "wg_symnorm_long_row": (ctypes.c_int, []),
     "wg_symnorm_aggregate": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
                                             c_vp]),
+    "wg_gated_symnorm_long_row": (ctypes.c_int, []),
+    "wg_gated_symnorm_forward": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64]
+                                 + [c_vp] * 8 + [c_vp]),
+    "wg_gets_head_backward": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_vp] * 8 + [c_vp]),
+    "wg_gated_symnorm_transposed": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64]
+                                    + [c_vp] * 4 + [c_vp]),
     "wg_simcalib_max_d": (ctypes.c_int, []),
     "wg_simcalib_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp]),
     "wg_simcalib_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_vp, c_vp]),

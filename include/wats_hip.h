@@ -640,6 +640,84 @@ int wg_symnorm_aggregate(int64_t n, int64_t nnz, const int64_t* indptr, const in
                          void* stream);
 
 /* -------------------------------------------------------------------------
+ * Section 8(f): the gated mixture of graph experts of the GETS calibrator
+ * (reference calibration/GETS.py).  Each of its E experts ends in a PyG GCNConv;
+ * forward stacks the E aggregated (N, C) outputs, multiplies them by gates that
+ * are exact zeros outside a row's top-k selection and sums.  The gate belongs
+ * to the destination row, so it commutes with the aggregation, and the three
+ * entries below never build an (N, E, C) tensor of aggregated outputs.
+ *
+ * indptr / indices / dinv / long_rows: exactly what wg_symnorm_aggregate takes
+ * (the canonical CSR by destination with one self loop per node, dinv =
+ * in-degree^-1/2), with rows of at least wg_gated_symnorm_long_row() entries
+ * (128) listed ascending.  A listed row that is not long is harmless, and a
+ * long row that is not listed is still computed (by one sub-group: slowly).
+ * All row-major: z (n, E, C) float32, each expert's last linear map; sel
+ * (n, k) int32, the selected experts of a row, distinct, in [0, E); gate
+ * (n, k) float32, their weights; bias (E, C) float32 or NULL; logits (n, C)
+ * float32.
+ *
+ * wg_gated_symnorm_forward replaces the last GCNConv's propagation of every
+ * expert (GETS.py:86-92 through :402-407) and GETS.py:410-417.  For row i and
+ * slot s, with e = sel[i, s]:
+ *   acc_s = sum_{p in [indptr[i], indptr[i+1])} dinv[j_p] * z[j_p, e, :]
+ *   O_s   = dinv[i] * acc_s + bias[e]           T = sum_s gate[i, s] * O_s
+ *   sp    = T > 20 ? T : log1p(exp(T))          (torch's softplus)
+ *   out   = log_softmax(logits[i] * sp)         out (n, C)
+ * t_save (n, C) = T and o_save (n, k, C) = O_s are what the backward needs;
+ * both NULL for inference.  A slice that a row did not select is never read: a
+ * NaN in it does not reach that row (the reference's 0 * NaN would).  A row
+ * with an empty range gives T = sum_s gate * bias.
+ *
+ * wg_gets_head_backward replaces autograd's backward of GETS.py:410-417, row by
+ * row without the graph, from g_out = d loss / d out:
+ *   g_cal    = g_out - exp(out) * sum_c g_out
+ *   g_logits = g_cal * sp(T)
+ *   g_t      = g_cal * logits * (T > 20 ? 1 : sigmoid(T))
+ *   g_gate[i, s] = sum_c g_t[i, c] * o_save[i, s, c]     (the float64 g_t)
+ * with T read from t_save.  None of these reads the gate, so it is no argument.
+ *
+ * wg_gated_symnorm_transposed replaces the backward of the stacked propagation
+ * w.r.t. its inputs, on the transposed structure (wg_csr_transpose_map, with
+ * the long rows of t_indptr):
+ *   g_z[j, e, :] = dinv[j] * sum_{i : j in row i} dinv[i] *
+ *                  (gate[i, s] if sel[i, s] == e for a slot s, else 0) * g_t[i, :]
+ * It writes all E slices of every row, exact zeros where no gathering row
+ * selected e (a NaN in g_t[i] reaches only the experts that row i selected).
+ * The gradient w.r.t. bias is a small (E, n) x (n, C) product left to the
+ * caller.
+ *
+ * Arithmetic: every product, sum, exp and log is float64 (the row's maximum and
+ * sum of the log_softmax go across the sub-group in float64), every output is
+ * rounded once to float32; the order of every sum is fixed by the row, C and the
+ * launch shape; no float atomics: the same input gives the same bits.  16-byte
+ * loads when C % 4 == 0 and every float buffer of the call is 16-byte aligned,
+ * dword loads otherwise.  Column ids, row ranges, listed rows and the ids in
+ * sel are checked on the device in the bounds-checked variant only; every
+ * other argument before any device call: a negative size, C < 1, E < 1, k < 1,
+ * k > E, n_long > n, a NULL pointer other than those named nullable (indices
+ * with nnz > 0, long_rows with n_long > 0), only one of t_save / o_save, an
+ * output that aliases an input or another output: WG_ERR_INVALID; C > 256
+ * (the row's softmax needs the whole row in one sub-group), E > 4 (k > 4 in
+ * wg_gets_head_backward), n or nnz above int32: WG_ERR_UNSUPPORTED.  n == 0 is
+ * WG_OK with no launch.  Asynchronous, allocate nothing, may be captured.
+ * ---------------------------------------------------------------------- */
+int wg_gated_symnorm_long_row(void);
+int wg_gated_symnorm_forward(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                             int64_t n_long, const int32_t* long_rows, const float* dinv, int64_t C,
+                             int64_t E, int64_t k, const float* z, const int32_t* sel,
+                             const float* gate, const float* bias, const float* logits, float* out,
+                             float* t_save, float* o_save, void* stream);
+int wg_gets_head_backward(int64_t n, int64_t C, int64_t k, const float* g_out, const float* out,
+                          const float* logits, const float* t_save, const float* o_save,
+                          float* g_logits, float* g_t, float* g_gate, void* stream);
+int wg_gated_symnorm_transposed(int64_t n, int64_t nnz, const int64_t* t_indptr,
+                                const int32_t* t_indices, int64_t n_long, const int32_t* long_rows,
+                                const float* dinv, int64_t C, int64_t E, int64_t k,
+                                const int32_t* sel, const float* gate, const float* g_t, float* g_z,
+                                void* stream);
+
+/* -------------------------------------------------------------------------
  * Section 8(f): the similarity temperature of the SimCalib calibrator
  * (reference calibration/SimCalib.py:49-58, 91-105).  The reference builds the
  * (N, N_val) cosine matrix of the latent rows against the validation bank, its
