@@ -24,7 +24,9 @@ weighted_propagate / homophily_weights (the edge-weight calibrator: its edge MLP
 float32 matrix cores with no (E, k) tensor, and the base model's propagation with the edge values as an argument),
 GETSCalibrator / GCNExpert / gated_sym_norm_head / calibrate_with_gets (the mixture-of-graph-experts calibrator: the
 last propagation of every expert, the top-k gated mixture, softplus and log_softmax as one HIP pass that reads only
-the selected slices, no (N, E, C) tensor of aggregated outputs).
+the selected slices, no (N, E, C) tensor of aggregated outputs), Calib_FGA / flip_select / target_logits (the
+reference's calibration attack as a drop-in class on the sparse path: the flip selection in one HIP pass and the
+candidate's logits from the 2-hop ball of the target).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -54,6 +56,15 @@ from .gcn import (  # noqa: F401
 from .head import wats_head  # noqa: F401
 from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
 from .flips import FlippedAdjacency  # noqa: F401
+from .attack import (  # noqa: F401
+    Calib_FGA,
+    flip_select,
+    kl_divergence_target,
+    kl_divergence_with_uniform,
+    overconfidence_objective,
+    target_logits,
+    underconfidence_objective,
+)
 from .gats import (  # noqa: F401
     GATS,
     AttentionGraph,

@@ -89,6 +89,12 @@ SIGNATURES = {
     "wg_flip_cols": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "wg_csr_patch": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_i64, ctypes.POINTER(c_i64), c_vp]),
+    "wg_flip_select_workspace": (ctypes.c_int, [ctypes.POINTER(c_i64)]),
+    "wg_flip_select": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wg_target_long_row": (ctypes.c_int, []),
+    "wg_target_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                        c_vp, c_vp, c_vp, c_vp]),
     "wg_coo_capacity": (ctypes.c_int, [c_i64, c_i64, c_u32, ctypes.POINTER(c_i64)]),
     "wg_coo_to_csr": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_u32, c_vp, c_vp, c_vp, c_i64,
                                      ctypes.POINTER(c_i64), c_vp]),

@@ -1,0 +1,572 @@
+"""``Calib_FGA`` of the reference (``calib_attack/calib_fga.py``) on the sparse path (DESIGN.md 4.3 "Attack step").
+
+Same class name, constructor, method names, positional order and keywords as the reference, so an attack script
+switches over by changing the import.  One step is
+
+* one forward of the surrogate with ``EdgeProbe.for_target(n, t)`` and ``torch.autograd.grad`` at ``probe.delta``
+  for the loss and, where the reference reranks, for ``p_max`` and ``p_smax`` (``calib_fga.py:877-890``);
+* :func:`flip_select` (``wg_flip_select``, ``csrc/attack.hip``): the scores of ``:880-897`` and their argmax in one
+  pass, without a dense row of the adjacency;
+* the flip as a ``with_flips`` view of the adjacency the attack started from;
+* the candidate's logits: :func:`target_logits` (``wg_target_logits``: the 2-hop ball of ``t`` only) when the
+  surrogate is a bare ``SparseCompatibleGCN`` or a ``WATS`` over one and the graph is unweighted, else one no-grad
+  forward through the view.
+
+The adjacency of a step is the start adjacency plus a *toggle set*: the partners ``j`` of ``t`` whose entries
+``(t, j)`` / ``(j, t)`` have been flipped an odd number of times.  The reference's quirks are kept: the rerank reads
+the row gradient only, compares with ``> 0`` and masks the self entry with ``-10``; the "beam" pops up to
+``beam_width`` members that each yield one child, so it holds one; ``attack`` / ``rerank*`` stop at the first label
+change, the beam method does not; the best-so-far rules use ``<=`` / ``>=`` / ``<`` as written per method;
+``strategy='max'`` of ``attack`` calls ``kl_divergence_target`` with two arguments and raises ``TypeError``, as the
+reference does.  Not kept: ``check_adj``'s dense ``(N, N)`` symmetry test.
+
+Results: ``flips`` (the partners in the order flipped), ``best_flips`` (the toggle set that gave the best
+confidence, ascending), ``modified_op`` (that adjacency as a view: ``.materialize()`` / ``.to_graph()``),
+``modified_adj`` (a dense tensor when ``ori_adj`` was dense; otherwise ``AttributeError``), ``trace`` (one dict per
+evaluated candidate: partner, logits row, label, confidence).
+"""
+from __future__ import annotations
+
+import ctypes
+import heapq
+import time
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from ._lib import check, ptr
+from .flips import FlippedAdjacency
+from .gcn import EdgeProbe, RowNormalizedAdjacency, SparseCompatibleGCN
+from .laplacian import require_gpu, stream_handle
+
+try:  # optional: the reference's verbose tables
+    from tabulate import tabulate as _tabulate
+except ImportError:  # pragma: no cover
+    _tabulate = None
+
+
+# ------------------------------------------------------------------------------------------------ the loss functions
+def _target_probs(logits, labels):
+    probs = F.softmax(logits, dim=1)
+    return probs, probs[torch.arange(len(labels)), labels]
+
+
+def underconfidence_objective(logits, labels):
+    """``-mean(p_label - max of the other classes' p)`` (``calib_attack_loss.py:158-178``)."""
+    probs, own = _target_probs(logits, labels)
+    keep = torch.ones_like(probs)
+    keep[torch.arange(len(labels)), labels] = 0
+    others, _ = torch.max(probs * keep, dim=1)
+    return -torch.mean(own - others)
+
+
+def overconfidence_objective(logits, labels):
+    """``-mean(1 - p_label)`` (``calib_attack_loss.py:181-208``)."""
+    _, own = _target_probs(logits, labels)
+    return -torch.mean(1 - own)
+
+
+def kl_divergence_with_uniform(logits, labels):
+    """``-KL(uniform || softmax(logits))``, batch mean (``calib_attack_loss.py:68-79``); ``labels`` is unused."""
+    probs = F.softmax(logits, dim=1)
+    uniform = torch.full_like(probs, 1.0 / logits.shape[1])
+    return -F.kl_div(probs.log(), uniform, reduction='batchmean')
+
+
+def kl_divergence_target(logits, target_label, res_gt):
+    """``-KL(target distribution || softmax(logits))`` with the reference's four-way target distribution
+    (``calib_attack_loss.py:101-154``)."""
+    probs = F.softmax(logits, dim=1)
+    predicted = torch.argmax(probs, dim=1)
+    n_classes = logits.shape[1]
+    dist = torch.zeros_like(probs)
+    for i in range(logits.shape[0]):
+        if predicted[i] == target_label[i]:
+            if res_gt[i] == target_label[i]:
+                dist[i] = torch.full((n_classes,), 1.0 / n_classes, dtype=probs.dtype, device=probs.device)
+            else:
+                dist[i, target_label[i]] = 1.0
+        elif res_gt[i] != target_label[i]:
+            dist[i] = torch.full((n_classes,), 1.0 / (n_classes - 1), dtype=probs.dtype, device=probs.device)
+            dist[i, target_label[i]] = 0.0
+        else:
+            dist[i, target_label[i]] = 0.5
+            dist[i, predicted[i]] = 0.5
+    return -F.kl_div(probs.log(), dist, reduction='batchmean')
+
+
+def _restore_loss(output, label):
+    return -F.nll_loss(output, label)
+
+
+# ------------------------------------------------------------------------------------------------ the two kernels
+def select_workspace(device) -> torch.Tensor:
+    """The buffer ``wg_flip_select`` merges its workgroups' partial lists in (reusable across calls on a stream)."""
+    nbytes = ctypes.c_int64(0)
+    check(_lib.load().wg_flip_select_workspace(ctypes.byref(nbytes)), "flip_select_workspace")
+    return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+
+
+def flip_select(n: int, t: int, grad_loss: torch.Tensor, indptr: torch.Tensor, indices: torch.Tensor,
+                values: torch.Tensor | None = None, toggled: torch.Tensor | None = None,
+                grad_pmax: torch.Tensor | None = None, grad_psmax: torch.Tensor | None = None,
+                p_top2: torch.Tensor | None = None, topk: int = 1, n_workgroups: int = 0, return_scores: bool = False,
+                workspace: torch.Tensor | None = None):
+    """``wg_flip_select``: ``(best_ids int32 [topk], best_scores float32 [topk])`` and, with ``return_scores``, the
+    score vector ``[n]``.  Tensors are taken as they are (device float32 / int64 / int32, any 4-byte alignment)."""
+    device = require_gpu(grad_loss.device if grad_loss.is_cuda else None)
+    lib = _lib.load()
+    best_ids = torch.empty(topk, dtype=torch.int32, device=device)
+    best_scores = torch.empty(topk, dtype=torch.float32, device=device)
+    scores = torch.empty(n, dtype=torch.float32, device=device) if return_scores else None
+    if workspace is None:
+        workspace = select_workspace(device)
+    n_toggled = 0 if toggled is None else int(toggled.numel())
+    with torch.cuda.device(device):
+        check(lib.wg_flip_select(n, t, ptr(grad_loss), ptr(grad_pmax), ptr(grad_psmax), ptr(p_top2), ptr(indptr),
+                                 ptr(indices) if indices is not None and indices.numel() else None, ptr(values),
+                                 n_toggled, ptr(toggled) if n_toggled else None, topk, n_workgroups, ptr(workspace),
+                                 ptr(scores), ptr(best_ids), ptr(best_scores), stream_handle(device)), "flip_select")
+    return (best_ids, best_scores, scores) if return_scores else (best_ids, best_scores)
+
+
+def target_logits(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.Tensor, b1: torch.Tensor,
+                  W2: torch.Tensor, b2: torch.Tensor, t: int, candidates) -> torch.Tensor:
+    """``wg_target_logits``: the ``(B, C)`` logits of node ``t`` of the two-layer base model under the candidate
+    toggle sets ``candidates`` (a list of lists of partners, or ``(cand_ptr, cand_ids)`` int32 device tensors that
+    were checked by the caller).  ``z = x @ W1.T``."""
+    device = require_gpu(z.device if z.is_cuda else None)
+    if isinstance(candidates, tuple):
+        cand_ptr, cand_ids = candidates
+    else:
+        ptrs, ids = [0], []
+        for S in candidates:
+            S = [int(j) for j in S]
+            if any(b <= a for a, b in zip(S, S[1:])) or any(j == int(t) or not 0 <= j < n for j in S):
+                raise ValueError("a candidate's partners must be ascending, distinct, inside [0, n) and not the target")
+            ids += S
+            ptrs.append(len(ids))
+        cand_ptr = torch.tensor(ptrs, dtype=torch.int32).to(device)
+        cand_ids = torch.tensor(ids, dtype=torch.int32).to(device)
+    B, C, Hd = int(cand_ptr.numel()) - 1, int(W2.shape[0]), int(z.shape[1])
+    if z.shape[0] != n or W2.shape[1] != Hd or b1.numel() != Hd or b2.numel() != C:
+        raise ValueError("target_logits: z (n, Hd), b1 [Hd], W2 (C, Hd), b2 [C] expected")
+    out = torch.empty((B, C), dtype=torch.float32, device=device)
+    nnz = int(indices.numel())
+    with torch.cuda.device(device):
+        check(_lib.load().wg_target_logits(n, nnz, ptr(indptr), ptr(indices) if nnz else None, Hd, ptr(z), ptr(b1),
+                                           ptr(W2), ptr(b2), C, int(t), B, ptr(cand_ptr),
+                                           ptr(cand_ids) if cand_ids.numel() else None, ptr(out),
+                                           stream_handle(device)), "target_logits")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the attack
+class Calib_FGA(torch.nn.Module):
+    """The reference's calibrated fast gradient attack on a sparse surrogate.  ``local_eval=False`` evaluates every
+    candidate by a forward through the flipped view (always the case for surrogates other than
+    ``SparseCompatibleGCN`` or ``WATS`` over it, and for valued graphs)."""
+
+    def __init__(self, model, feature_shape=None, attack_features=False, device=None, logits=True, *,
+                 local_eval: bool = True, record_scores: bool = False):
+        super().__init__()
+        assert not attack_features, "not support attacking features"
+        self.surrogate = model
+        self.attack_structure, self.attack_features = True, False
+        self.device = require_gpu(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.local_eval, self.record_scores = bool(local_eval), bool(record_scores)
+        self.modified_features = None
+        self.modified_op = None
+        self.flips, self.best_flips, self.trace = [], [], []
+        self._z_key = self._z = None
+        self._workspace = None
+
+    def __getattr__(self, name):
+        if name == "modified_adj":
+            raise AttributeError("modified_adj is a dense (N, N) tensor and exists only when ori_adj was dense; "
+                                 "read modified_op (.materialize() gives an operator, .to_graph() a CSR)")
+        return super().__getattr__(name)
+
+    # -------------------------------------------------------------------------------------------- logging
+    @staticmethod
+    def _log_attack_header(strategy, target_node, budget, original_label, original_confidence):
+        print("\n" + "=" * 80)
+        print(f"[{strategy.upper()}][Node {target_node}] Starting attack | budget={budget}")
+        print(f"Baseline label={original_label} | confidence={original_confidence:.4f}")
+        print("-" * 80)
+
+    @staticmethod
+    def _log_iteration(strategy, target_node, step, budget, action, edge_idx, prev_confidence, new_confidence,
+                       baseline_confidence, predicted_label, loss=None, log_rows=None):
+        step_delta, total_delta = new_confidence - prev_confidence, new_confidence - baseline_confidence
+        message = (f"[{strategy.upper()}][Node {target_node}][Step {step}/{budget}] "
+                   f"{action} edge ({target_node}, {edge_idx}) | pred {predicted_label} | "
+                   f"conf {new_confidence:.4f} (Δ step {step_delta:+.4f}, Δ total {total_delta:+.4f})")
+        if loss is not None:
+            message += f" | loss {loss:.4f}"
+        print(message)
+        if log_rows is not None:
+            log_rows.append([step, action, predicted_label, f"{new_confidence:.4f}", f"{step_delta:+.4f}",
+                             f"{total_delta:+.4f}", f"{loss:.4f}" if loss is not None else "-"])
+
+    @staticmethod
+    def _log_attack_summary(strategy, target_node, used, budget, original_label, final_label, baseline_confidence,
+                            final_confidence):
+        status = "preserved" if final_label == original_label else "CHANGED"
+        print(f"[{strategy.upper()}][Node {target_node}] Perturbations used: {used}/{budget}")
+        print(f"Label: {original_label} -> {final_label} ({status})")
+        print(f"Confidence: {baseline_confidence:.4f} -> {final_confidence:.4f} "
+              f"(Δ {final_confidence - baseline_confidence:+.4f})")
+        print("=" * 80 + "\n")
+
+    @staticmethod
+    def _print_table(rows, headers):
+        if _tabulate is not None:
+            print(_tabulate(rows, headers=headers, tablefmt="grid"))
+        else:
+            print(" | ".join(headers))
+            for row in rows:
+                print(" | ".join(str(v) for v in row))
+
+    # -------------------------------------------------------------------------------------------- one attack's state
+    def _begin(self, ori_features, ori_adj, target_node):
+        """The start adjacency as an operator or view, its CSR, and what the fast evaluation needs."""
+        self._dense = None
+        self.__dict__.pop("modified_adj", None)
+        if torch.is_tensor(ori_adj):
+            self._dense = ori_adj.detach()
+            start = RowNormalizedAdjacency.from_dense(self._dense.to(self.device))
+        elif isinstance(ori_adj, RowNormalizedAdjacency):
+            start = ori_adj
+        else:
+            raise TypeError("ori_adj must be a dense tensor, a RowNormalizedAdjacency or a FlippedAdjacency")
+        self._start = start
+        self._n, self._t = int(start.n), int(target_node)
+        if not 0 <= self._t < self._n:
+            raise ValueError(f"target {self._t} outside [0, {self._n})")
+        self._x = ori_features.detach().to(start.device)
+        self._csr = start.csr() if isinstance(start, FlippedAdjacency) else (start.indptr, start.indices, start.values)
+        self._probe = EdgeProbe.for_target(self._n, self._t, device=start.device)
+        self.flips, self.best_flips, self.trace = [], [], []
+        self._last_scores = None
+        self.surrogate.eval()
+        if self._workspace is None:
+            self._workspace = select_workspace(self.device)
+        self._local = self._local_model()
+
+    def _local_model(self):
+        """(gcn, wats or None) when ``wg_target_logits`` applies, else None."""
+        if not self.local_eval:
+            return None
+        model, wats = self.surrogate, None
+        from .WATS import WATS
+        if isinstance(model, WATS) and not getattr(model, "fused_head", False):
+            model, wats = model.base_model, model
+        if type(model) is not SparseCompatibleGCN:
+            return None
+        if model.gc1.out_features > 256 or model.gc2.out_features > 256:
+            return None
+        values = self._csr[2]
+        if values is not None and not bool((values == 1).all()):
+            return None     # a valued graph: the view path
+        return model, wats
+
+    def _view(self, toggles):
+        toggles = sorted(toggles)
+        return self._start.with_flips([self._t] * len(toggles), toggles)
+
+    def _forward_probe(self, toggles):
+        adj = self._view(toggles) if toggles else self._start
+        return self.surrogate(self._x, adj, probe=self._probe)[[self._t]]
+
+    def _grad(self, value, **kw):
+        g = torch.autograd.grad(value, self._probe.delta, **kw)[0]
+        return torch.zeros_like(self._probe.delta) if g is None else g.contiguous()
+
+    def _select(self, toggles, grad_loss, rerank=None):
+        """The partner to flip (``calib_fga.py:880-898``) from the probe's gradients."""
+        indptr, indices, values = self._csr
+        tog = torch.tensor(sorted(toggles), dtype=torch.int32).to(self.device) if toggles else None
+        gp = gs = top2 = None
+        if rerank is not None:
+            top2, gp, gs = rerank
+        res = flip_select(self._n, self._t, grad_loss, indptr, indices, values, tog, gp, gs, top2, topk=1,
+                          return_scores=self.record_scores, workspace=self._workspace)
+        self._last_scores = res[2].cpu() if self.record_scores else None
+        return int(res[0][0])
+
+    def _rerank_terms(self, output):
+        """``p_max`` / ``p_smax`` and their gradients (``calib_fga.py:886-890``)."""
+        probabilities = F.softmax(output, dim=1)
+        top2 = torch.topk(probabilities, 2, dim=1)[0][0]
+        g_pmax = self._grad(top2[0], retain_graph=True)
+        g_psmax = self._grad(top2[1], retain_graph=True)
+        return top2.detach().contiguous(), g_pmax, g_psmax
+
+    def _evaluate(self, toggles):
+        """The surrogate's output row ``[[t]]`` on the start adjacency with ``toggles`` flipped, without gradient."""
+        with torch.no_grad():
+            if self._local is None:
+                return self.surrogate(self._x, self._view(toggles) if toggles else self._start)[[self._t]]
+            model, wats = self._local
+            w1 = model.gc1.weight
+            key = (self._x.data_ptr(), self._x._version, tuple(self._x.shape), w1.data_ptr(), w1._version)
+            if self._z_key != key:
+                self._z, self._z_key = (self._x.to(torch.float32) @ w1.t()).contiguous(), key
+            out = target_logits(self._n, self._csr[0], self._csr[1], self._z, model.gc1.bias.detach(),
+                                model.gc2.weight.detach().contiguous(), model.gc2.bias.detach(), self._t,
+                                [sorted(toggles)])
+            if wats is not None:
+                out = F.log_softmax(out / wats.temperatures()[self._t], dim=1)
+            return out
+
+    @staticmethod
+    def _toggle(toggles, j):
+        """The toggle set after one more flip of partner ``j`` (a second flip of the same edge cancels the first)."""
+        new = set(toggles)
+        new.symmetric_difference_update({j})
+        return new
+
+    def _is_edge(self, toggles, j):
+        """Whether (t, j) is an entry of the current adjacency (unit graphs: for the verbose "Added" / "Removed")."""
+        indptr, indices, values = self._csr
+        s, e = (int(v) for v in indptr[self._t:self._t + 2])
+        present = bool((indices[s:e] == j).any())
+        return present != (j in toggles)
+
+    def _finish(self, best_toggles):
+        self.best_flips = sorted(best_toggles)
+        self.modified_op = self._view(self.best_flips)
+        if self._dense is not None:
+            adj = self._dense.clone()
+            t = self._t
+            for j in self.best_flips:                        # calib_fga.py:901-904
+                v = -2 * adj[t][j] + 1
+                adj[t][j] += v
+                adj[j][t] += v
+            self.__dict__["modified_adj"] = adj
+        with torch.no_grad():
+            final_output = self.surrogate(self._x, self.modified_op).detach()[[self._t]]
+        final_label = int(final_output.argmax(dim=1).item())
+        return final_label, float(F.softmax(final_output, dim=1)[0, final_label].item())
+
+    def _record(self, j, new_output, label, confidence):
+        self.flips.append(j)
+        self.trace.append(dict(partner=j, logits=new_output.detach().cpu()[0], label=label, confidence=confidence,
+                               scores=self._last_scores))
+
+    # -------------------------------------------------------------------------------------------- the four methods
+    def attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy, *, target_label=0, res_gt=None,
+               verbose=False, **kwargs):
+        """``calib_fga.py:128-344``: flip the best-scoring edge while the label holds; strategies ``over``,
+        ``under``, ``under_kl``, ``target``, ``max``."""
+        display_strategy = strategy
+        self._begin(ori_features, ori_adj, target_node)
+        original_output = self._evaluate_start()
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for Calib_FGA attacks")
+        res_gt = res_gt[[target_node]].to(self.device)
+        original_label = original_output.argmax(1)
+        original_label_item = int(original_label.item())
+        best_confidence = F.softmax(original_output, dim=1)[0, original_label_item].item()
+        initial_confidence = best_confidence
+        self._log_attack_header(display_strategy, target_node, n_perturbations, original_label_item, initial_confidence)
+        if strategy == 'over':
+            criterion = overconfidence_objective
+        elif strategy == 'under':
+            criterion = underconfidence_objective
+        elif strategy == 'under_kl':
+            strategy = "under"
+            criterion = kl_divergence_with_uniform
+        elif strategy == 'target':
+            criterion = kl_divergence_target
+        elif strategy == 'max':
+            criterion = kl_divergence_target
+            target_label = original_label
+        else:
+            raise ValueError(f"Unknown strategy: {strategy}")
+        toggles, best = set(), set()
+        attack_times = 0
+        table_rows = [] if verbose else None
+        for i in range(n_perturbations):
+            output = self._forward_probe(toggles)
+            current_label = output.argmax(dim=1)
+            prev_confidence = F.softmax(output.detach(), dim=1)[0, current_label].item() if verbose else None
+            if strategy != 'target':
+                loss = criterion(output, current_label)     # 'max': TypeError, as in the reference
+            else:
+                loss = criterion(output, torch.tensor([target_label], device=output.device), res_gt)
+            j = self._select(toggles, self._grad(loss, allow_unused=True))
+            added = not self._is_edge(toggles, j) if verbose else None
+            toggles = self._toggle(toggles, j)
+            new_output = self._evaluate(toggles)
+            new_label = new_output.argmax(dim=1)
+            if new_label != original_label:
+                self._record(j, new_output, int(new_label.item()), float("nan"))
+                print(f"[{display_strategy.upper()}][Node {target_node}] "
+                      f"Early stop at step {i + 1}: label flipped to {int(new_label.item())}")
+                break
+            attack_times += 1
+            predicted_label = int(new_label.item())
+            current_confidence = F.softmax(new_output, dim=1)[0, predicted_label].item()
+            self._record(j, new_output, predicted_label, current_confidence)
+            if strategy == 'over' and current_confidence >= best_confidence:
+                best_confidence, best = current_confidence, set(toggles)
+            elif strategy == 'under' and current_confidence <= best_confidence:
+                best_confidence, best = current_confidence, set(toggles)
+            elif strategy == 'target':
+                if (target_label == original_label and target_label == res_gt.item()) or \
+                   (target_label != original_label and target_label == res_gt.item()):
+                    if current_confidence <= best_confidence:
+                        best_confidence, best = current_confidence, set(toggles)
+                elif current_confidence >= best_confidence:
+                    best_confidence, best = current_confidence, set(toggles)
+            if verbose:
+                self._log_iteration(display_strategy, target_node, i + 1, n_perturbations,
+                                    "Added" if added else "Removed", j, prev_confidence, current_confidence,
+                                    initial_confidence, predicted_label, loss.item(), log_rows=table_rows)
+        kwargs["n_perturb"].append(attack_times)
+        kwargs["best_conf"].append(best_confidence)
+        final_label, final_confidence = self._finish(best)
+        if verbose and table_rows:
+            self._print_table(table_rows, ["Step", "Action", "Pred", "Conf", "Δ step", "Δ total", "Loss"])
+        self._log_attack_summary(display_strategy, target_node, attack_times, n_perturbations, original_label_item,
+                                 final_label, initial_confidence, final_confidence)
+
+    def _evaluate_start(self):
+        with torch.no_grad():
+            return self.surrogate(self._x, self._start).detach()[[self._t]]
+
+    def rerank_attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy, *, target_label=0,
+                      res_gt=None, verbose=False, **kwargs):
+        """``calib_fga.py:346-540``: ``attack`` with the label-flip rerank (``under`` only)."""
+        if strategy != 'under':
+            raise ValueError(f"rerank_attack only supports 'under' strategy, got '{strategy}'")
+        self._greedy(ori_features, ori_adj, target_node, n_perturbations, strategy, res_gt, verbose, kwargs,
+                     hybrid=False)
+
+    def rerank_hybridloss_attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy, *,
+                                 target_label=0, res_gt=None, verbose=False, **kwargs):
+        """``calib_fga.py:542-749``: the rerank with the hybrid loss (``under`` only)."""
+        if strategy != 'under':
+            raise ValueError(f"rerank_hybridloss_attack only supports 'under' strategy, got '{strategy}'")
+        self._greedy(ori_features, ori_adj, target_node, n_perturbations, strategy, res_gt, verbose, kwargs,
+                     hybrid=True)
+
+    def _hybrid_step(self, toggles, original_label, hybrid):
+        """One scored step of the rerank methods: (partner, loss, loss mode, output)."""
+        output = self._forward_probe(toggles)
+        current_label = output.argmax(dim=1)
+        same = bool(current_label == original_label)
+        if same or not hybrid:
+            loss, mode = kl_divergence_with_uniform(output, current_label), "calib"
+        else:
+            loss, mode = _restore_loss(output, original_label), "restore"
+        grad = self._grad(loss, retain_graph=True)
+        rerank = self._rerank_terms(output) if (same or not hybrid) else None
+        return self._select(toggles, grad, rerank), loss, mode, output
+
+    def _greedy(self, ori_features, ori_adj, target_node, n_perturbations, strategy, res_gt, verbose, kwargs, hybrid):
+        display_strategy = strategy
+        self._begin(ori_features, ori_adj, target_node)
+        original_output = self._evaluate_start()
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for Calib_FGA attacks")
+        original_label = original_output.argmax(1)
+        original_label_item = int(original_label.item())
+        best_confidence = F.softmax(original_output, dim=1)[0, original_label_item].item()
+        initial_confidence = best_confidence
+        self._log_attack_header(display_strategy, target_node, n_perturbations, original_label_item, initial_confidence)
+        toggles, best = set(), set()
+        attack_times = 0
+        table_rows = [] if verbose else None
+        for i in range(n_perturbations):
+            j, loss, mode, output = self._hybrid_step(toggles, original_label, hybrid)
+            prev_confidence = F.softmax(output.detach(), dim=1)[0].max().item() if verbose else None
+            added = not self._is_edge(toggles, j) if verbose else None
+            toggles = self._toggle(toggles, j)
+            new_output = self._evaluate(toggles)
+            new_label = new_output.argmax(dim=1)
+            if new_label != original_label:
+                self._record(j, new_output, int(new_label.item()), float("nan"))
+                print(f"[{display_strategy.upper()}][Node {target_node}] "
+                      f"Early stop at step {i + 1}: label flipped to {int(new_label.item())}")
+                break
+            predicted_label = int(new_label.item())
+            current_confidence = F.softmax(new_output, dim=1)[0, predicted_label].item()
+            self._record(j, new_output, predicted_label, current_confidence)
+            attack_times += 1
+            if current_confidence <= best_confidence:
+                best_confidence, best = current_confidence, set(toggles)
+            if verbose:
+                action = "Added" if added else "Removed"
+                if hybrid:
+                    action = f"{action} [{mode}]"
+                self._log_iteration(display_strategy, target_node, i + 1, n_perturbations, action, j, prev_confidence,
+                                    current_confidence, initial_confidence, predicted_label, loss.item(),
+                                    log_rows=table_rows)
+        kwargs["n_perturb"].append(attack_times)
+        kwargs["best_conf"].append(best_confidence)
+        final_label, final_confidence = self._finish(best)
+        if verbose and table_rows:
+            self._print_table(table_rows, ["Step", "Action", "Pred", "Conf", "Δ step", "Δ total", "Loss"])
+        self._log_attack_summary(display_strategy, target_node, attack_times, n_perturbations, original_label_item,
+                                 final_label, initial_confidence, final_confidence)
+
+    def flip_beam_hybridloss_attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy, *,
+                                    target_label=0, res_gt=None, verbose=False, **kwargs):
+        """``calib_fga.py:751-969``: the beam search with the hybrid loss and the rerank (``under`` only).  Each
+        iteration pops up to ``beam_width`` members and each yields one child, so the beam holds one member."""
+        if strategy != 'under':
+            raise ValueError(f"flip_beam_hybridloss_attack only supports 'under' strategy, got '{strategy}'")
+        display_strategy = strategy
+        self._begin(ori_features, ori_adj, target_node)
+        original_output = self._evaluate_start()
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for Calib_FGA attacks")
+        original_label = original_output.argmax(1)
+        original_label_item = int(original_label.item())
+        beam_width = kwargs.get('beam_width', 3)
+        initial_confidence = F.softmax(original_output, dim=1)[0, original_label_item].item()
+        self._log_attack_header(display_strategy, target_node, n_perturbations, original_label_item, initial_confidence)
+        seq = 0                                        # orders equal (confidence, count) pairs: the reference's queue
+        beam = [(initial_confidence, 0, seq, frozenset())]          # would compare tensors there and raise
+        best, best_confidence, attack_times = frozenset(), initial_confidence, 0
+        table_data = []
+        start_time = time.time()
+        for iteration in range(n_perturbations):
+            next_beam = []
+            for _ in range(beam_width):
+                if not beam:
+                    break
+                _, count, _, toggles = heapq.heappop(beam)
+                if count >= n_perturbations:
+                    continue
+                j, _, _, _ = self._hybrid_step(set(toggles), original_label, hybrid=True)
+                child = frozenset(self._toggle(toggles, j))
+                new_output = self._evaluate(child)
+                new_label = new_output.argmax(dim=1)
+                new_confidence = F.softmax(new_output, dim=1)[0, new_label].item()
+                self._record(j, new_output, int(new_label.item()), new_confidence)
+                seq += 1
+                heapq.heappush(next_beam, (new_confidence, count + 1, seq, child))
+                if new_label == original_label and new_confidence < best_confidence:
+                    best_confidence, best, attack_times = new_confidence, child, count + 1
+            beam = next_beam
+            table_data.append([iteration + 1, f"{initial_confidence:.4f}", f"{best_confidence:.4f}", attack_times])
+        elapsed_time = time.time() - start_time
+        if verbose:
+            self._print_table(table_data, ["Iteration", "Initial Confidence", "Best Confidence", "Perturbations"])
+            print(f"Attack completed in {elapsed_time:.4f} seconds")
+        kwargs["n_perturb"].append(attack_times)
+        kwargs["best_conf"].append(best_confidence)
+        if "runtime" in kwargs:
+            kwargs["runtime"].append(elapsed_time)
+        final_label, final_confidence = self._finish(best)
+        if final_label != original_label_item:
+            raise ValueError("Final label does not match original label!")
+        self._log_attack_summary(display_strategy, target_node, attack_times, n_perturbations, original_label_item,
+                                 final_label, initial_confidence, final_confidence)

@@ -866,6 +866,73 @@ int wg_edge_aggregate(int64_t n, int64_t nnz, const int64_t* indptr, const int32
 int wg_edge_pair_inv_distance(int64_t nnz, const int32_t* rows, const int32_t* cols, int64_t C,
                               int64_t n, const float* Q, double alpha, float* out, void* stream);
 
+/* -------------------------------------------------------------------------
+ * One step of the calibration attacks (calib_attack/calib_fga.py) on that path.
+ *
+ * wg_flip_select: the score of every partner j of the target t and the best
+ * topk of them (calib_fga.py:880-898), in one pass over n, all in float32,
+ * operation for operation what torch computes on the same tensors (no fused
+ * multiply-add):
+ *   a_j = the entry (t, j) of the base row (0 if absent; values NULL: 1);
+ *         j in toggled: a_j += 1 - 2 a_j
+ *   d_j = 1 - 2 a_j
+ *   s_j = (grad_loss[j] + grad_loss[n + j]) * d_j
+ *   with the rerank: c_j = ((p_top2[0] + grad_pmax[j] * d_j) - p_top2[1]) - grad_psmax[j] * d_j
+ *                    s_j *= (c_j > 0 ? 1 : -1)          (a NaN c_j: -1)
+ *   s_t = -10
+ * grad_loss / grad_pmax / grad_psmax are float32 [2 n] in the layout of the
+ * target probe -- d / d a[t, j] for all j, then d / d a[i, t] for all i; only
+ * the row half of grad_pmax / grad_psmax is read (div_pmax[target_node],
+ * calib_fga.py:893).  Both NULL: no rerank; one NULL: WG_ERR_INVALID.  p_top2:
+ * device float32 [2], read only with the rerank.  indptr / indices / values:
+ * the base CSR (row t is read); toggled: int32 [n_toggled] ascending, the
+ * partners whose entries (t, j) / (j, t) differ from the base (NULL when
+ * n_toggled == 0).  Outputs: scores [n] (nullable), best_ids int32 [topk],
+ * best_scores [topk], 1 <= topk <= 8, descending by score: a NaN ranks above
+ * every number (as torch.argmax has it), equal scores (-0 == +0) go by smaller
+ * index, a slot past n entries gets id -1 and score -inf.  The order is total,
+ * so the result does not depend on the grid: n_workgroups = 0 picks it
+ * (ceil(n / 256), at most 256), 1 .. 256 force it.  More than one workgroup
+ * leaves partial lists in workspace (wg_flip_select_workspace(&bytes), 8-byte
+ * aligned; may be NULL with one workgroup), merged by a second launch.
+ * Asynchronous, no allocation, capturable.  n == 0 is WG_OK with no launch.
+ * Ids are checked on the device in the bounds-checked variant only; every
+ * other argument before any device call.
+ *
+ * wg_target_logits: the logits of node t under B candidate adjacencies in one
+ * launch, for the two-layer base model (src/gnn/model.py) in eval mode on an
+ * unweighted canonical CSR.  z = x @ W1^T (n, Hd) is an argument: the kernel
+ * evaluates adj_norm (X W1^T) where the model computes (adj_norm X) W1^T.
+ * Candidate b toggles (t, j) and (j, t) for j in S_b = cand_ids[cand_ptr[b] ..
+ * cand_ptr[b + 1]) (int32, ascending, no t, no duplicates).  With N'(t) = N(t)
+ * delta S_b, N'(j) = N(j) delta {t} for j in S_b, N'(j) = N(j) otherwise and
+ * deg' = |N'| (0 -> 1, model.py:43-45):
+ *   y1_j = (1 / deg'_j) sum_{k in N'(j)} z_k          for j in N'(t)
+ *   h_j  = max(y1_j + b1, 0)
+ *   y2   = (1 / deg'_t) sum_{j in N'(t)} h_j
+ *   out[b] = W2 y2 + b2                               W2 (C, Hd), out (B, C)
+ * One workgroup per candidate; its waves take the j of N'(t) -- the base row's
+ * surviving entries in ascending order, then the added partners -- a j whose
+ * row has at least wg_target_long_row() (128) entries is shared by the whole
+ * workgroup.  Every sum and product is float64 in an order fixed by the rows,
+ * Hd and the launch shape; out is rounded once; no float atomics: the same
+ * input gives the same bits.  16-byte loads when Hd % 4 == 0 and z is 16-byte
+ * aligned.  1 <= Hd, C <= 256, B >= 1; n or nnz above int32:
+ * WG_ERR_UNSUPPORTED.  An empty S_b gives the base model's row t.
+ * Asynchronous, no allocation, capturable.
+ * ---------------------------------------------------------------------- */
+int wg_flip_select_workspace(int64_t* bytes);
+int wg_flip_select(int64_t n, int64_t t, const float* grad_loss, const float* grad_pmax,
+                   const float* grad_psmax, const float* p_top2, const int64_t* indptr,
+                   const int32_t* indices, const float* values, int64_t n_toggled,
+                   const int32_t* toggled, int32_t topk, int32_t n_workgroups, void* workspace,
+                   float* scores, int32_t* best_ids, float* best_scores, void* stream);
+int wg_target_long_row(void);
+int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                     int64_t Hd, const float* z, const float* b1, const float* W2, const float* b2,
+                     int64_t C, int64_t t, int64_t B, const int32_t* cand_ptr,
+                     const int32_t* cand_ids, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
