@@ -26,7 +26,8 @@ GETSCalibrator / GCNExpert / gated_sym_norm_head / calibrate_with_gets (the mixt
 last propagation of every expert, the top-k gated mixture, softplus and log_softmax as one HIP pass that reads only
 the selected slices, no (N, E, C) tensor of aggregated outputs), Calib_FGA / flip_select / target_logits (the
 reference's calibration attack as a drop-in class on the sparse path: the flip selection in one HIP pass and the
-candidate's logits from the 2-hop ball of the target).
+candidate's logits from the 2-hop ball of the target), Calib_IGA / iga_path_logits / iga_scores (the reference's
+integrated-gradients attack: its path integrals in closed form, all targets scored in one HIP pass over z and h).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -58,7 +59,10 @@ from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
 from .flips import FlippedAdjacency  # noqa: F401
 from .attack import (  # noqa: F401
     Calib_FGA,
+    Calib_IGA,
     flip_select,
+    iga_path_logits,
+    iga_scores,
     kl_divergence_target,
     kl_divergence_with_uniform,
     overconfidence_objective,

@@ -95,6 +95,12 @@ SIGNATURES = {
     "wg_target_long_row": (ctypes.c_int, []),
     "wg_target_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                         c_vp, c_vp, c_vp, c_vp]),
+    "wg_iga_max_topk": (ctypes.c_int, []),
+    "wg_iga_path_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_i64, c_i64, c_vp, c_i32, c_vp,
+                                                                                        c_vp, c_vp]),
+    "wg_iga_scores_workspace": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_iga_scores": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i32,
+                                     c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wg_coo_capacity": (ctypes.c_int, [c_i64, c_i64, c_u32, ctypes.POINTER(c_i64)]),
     "wg_coo_to_csr": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_u32, c_vp, c_vp, c_vp, c_i64,
                                      ctypes.POINTER(c_i64), c_vp]),

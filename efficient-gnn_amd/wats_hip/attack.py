@@ -570,3 +570,297 @@ class Calib_FGA(torch.nn.Module):
             raise ValueError("Final label does not match original label!")
         self._log_attack_summary(display_strategy, target_node, attack_times, n_perturbations, original_label_item,
                                  final_label, initial_confidence, final_confidence)
+
+
+# ------------------------------------------------------------------------------------------------ integrated gradients
+def iga_max_topk() -> int:
+    return int(_lib.load().wg_iga_max_topk())
+
+
+def iga_path_logits(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.Tensor, h: torch.Tensor,
+                    zsum: torch.Tensor, hsum: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor,
+                    targets: torch.Tensor, steps: int):
+    """``wg_iga_path_logits``: ``(logits (B, P, C) float32, state (B, P, 2 Hd + 2) float64)`` of the
+    ``P = 2 (steps + 1)`` path points of each target's row (``calib_iga.py:185-211``).  ``targets``: int32 device."""
+    device = require_gpu(z.device if z.is_cuda else None)
+    B, Hd, C, P = int(targets.numel()), int(z.shape[1]), int(W2.shape[0]), 2 * (int(steps) + 1)
+    if z.shape[0] != n or h.shape != z.shape or zsum.numel() != Hd or hsum.numel() != Hd or W2.shape[1] != Hd \
+            or b1.numel() != Hd or b2.numel() != C:
+        raise ValueError("iga_path_logits: z, h (n, Hd), zsum, hsum, b1 [Hd], W2 (C, Hd), b2 [C] expected")
+    logits = torch.empty((B, P, C), dtype=torch.float32, device=device)
+    state = torch.empty((B, P, 2 * Hd + 2), dtype=torch.float64, device=device)
+    nnz = int(indices.numel())
+    with torch.cuda.device(device):
+        check(_lib.load().wg_iga_path_logits(n, nnz, ptr(indptr), ptr(indices) if nnz else None, Hd, ptr(z), ptr(h),
+                                             ptr(zsum), ptr(hsum), ptr(b1), ptr(W2), ptr(b2), C, B, ptr(targets),
+                                             int(steps), ptr(logits), ptr(state), stream_handle(device)),
+              "iga_path_logits")
+    return logits, state
+
+
+def iga_scores_workspace(B: int, Hd: int, device) -> torch.Tensor:
+    nbytes = ctypes.c_int64(0)
+    check(_lib.load().wg_iga_scores_workspace(B, Hd, ctypes.byref(nbytes)), "iga_scores_workspace")
+    return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+
+
+def iga_scores(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.Tensor, h: torch.Tensor, b1: torch.Tensor,
+               W2: torch.Tensor, targets: torch.Tensor, steps: int, g_logits: torch.Tensor, state: torch.Tensor,
+               topk: int = 10, n_workgroups: int = 0, return_scores: bool = False, return_coeffs: bool = False,
+               workspace: torch.Tensor | None = None):
+    """``wg_iga_scores``: ``(best_ids int32 (B, topk), best_scores float32 (B, topk))`` and, on request, the score
+    matrix ``(B, n)`` and the coefficients ``(B, 2, 2 Hd + 1)`` float64 (``calib_iga.py:217-233`` for every target in
+    one pass over ``z`` and ``h``)."""
+    device = require_gpu(z.device if z.is_cuda else None)
+    B, Hd, C = int(targets.numel()), int(z.shape[1]), int(W2.shape[0])
+    P = 2 * (int(steps) + 1)
+    if tuple(g_logits.shape) != (B, P, C) or tuple(state.shape) != (B, P, 2 * Hd + 2) or h.shape != z.shape:
+        raise ValueError("iga_scores: g_logits (B, P, C) and state (B, P, 2 Hd + 2) of the same targets expected")
+    best_ids = torch.empty((B, topk), dtype=torch.int32, device=device)
+    best_scores = torch.empty((B, topk), dtype=torch.float32, device=device)
+    scores = torch.empty((B, n), dtype=torch.float32, device=device) if return_scores else None
+    coeffs = torch.empty((B, 2, 2 * Hd + 1), dtype=torch.float64, device=device) if return_coeffs else None
+    if workspace is None:
+        workspace = iga_scores_workspace(B, Hd, device)
+    nnz = int(indices.numel())
+    with torch.cuda.device(device):
+        check(_lib.load().wg_iga_scores(n, nnz, ptr(indptr), ptr(indices) if nnz else None, Hd, ptr(z), ptr(h), ptr(b1),
+                                        ptr(W2), C, B, ptr(targets), int(steps), ptr(g_logits), ptr(state), topk,
+                                        n_workgroups, ptr(workspace), ptr(coeffs), ptr(scores), ptr(best_ids),
+                                        ptr(best_scores), stream_handle(device)), "iga_scores")
+    out = (best_ids, best_scores)
+    if return_scores:
+        out += (scores,)
+    if return_coeffs:
+        out += (coeffs,)
+    return out
+
+
+def _criterion_rows(out, labels, strategy):
+    """``overconfidence_objective`` / ``underconfidence_objective`` applied to each row on its own (a batch of one:
+    the mean of one value, ``calib_iga.py:211-215``), summed over the rows.  Written as a sum so that a row's gradient
+    does not depend on how many rows share the call."""
+    probs, own = _target_probs(out, labels)
+    if strategy == 'over':
+        return -(1 - own).sum()
+    keep = torch.ones_like(probs)
+    keep[torch.arange(len(labels)), labels] = 0
+    others, _ = torch.max(probs * keep, dim=1)
+    return -(own - others).sum()
+
+
+class Calib_IGA(torch.nn.Module):
+    """``Calib_IGA`` of the reference (``calib_attack/calib_iga.py``) on the sparse path (DESIGN.md 4.3
+    "Integrated-gradient scores"): the same constructor, ``attack`` and ``calc_calibration_importance_edge``.
+
+    The reference's ``(N - 1) (steps + 1)`` dense forward / backward passes per target are, on the two-layer base
+    model, a closed form: ``wg_iga_path_logits`` evaluates the path points of row ``t``, the head and the criterion
+    run in torch autograd on those ``(P, C)`` logits, ``wg_iga_scores`` turns their gradient into the ``n`` scores and
+    the best partners, and one ``wg_target_logits`` call evaluates the prefixes of that ranking.
+
+    Surrogates: a bare ``SparseCompatibleGCN``, or a ``WATS`` over one without the fused head, on a unit graph.
+    Kept from the reference: the scores are computed once; the flips are cumulative and symmetric; the loop stops at
+    the first label change; ``>=`` for ``over`` and ``<=`` for ``under``.  Not kept: the stray ``print(i)``;
+    ``check_adj``'s dense test; a ranking that reaches ``t`` itself (its ``-10``) ends the loop there instead of
+    flipping the self entry.  Results as ``Calib_FGA`` names them: ``flips``, ``best_flips``, ``modified_op``,
+    ``modified_adj`` (dense input only), ``trace``."""
+
+    def __init__(self, model, nnodes=None, device=None):
+        super().__init__()
+        self.surrogate = model
+        self.nnodes = nnodes
+        self.attack_structure, self.attack_features = True, False
+        self.device = require_gpu(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.modified_op = None
+        self.target_node = None
+        self.flips, self.best_flips, self.trace = [], [], []
+        self._z_key = self._cache = None
+
+    def __getattr__(self, name):
+        if name == "modified_adj":
+            raise AttributeError("modified_adj is a dense (N, N) tensor and exists only when ori_adj was dense; "
+                                 "read modified_op (.materialize() gives an operator, .to_graph() a CSR)")
+        return super().__getattr__(name)
+
+    # -------------------------------------------------------------------------------------------- the graph's cache
+    def _model(self, values):
+        why = ("Calib_IGA on the sparse path needs {}: a path point has a dense row t, which no sparse operator holds, "
+               "so the scores come from the closed form of the two-layer base model on a unit graph")
+        model, wats = self.surrogate, None
+        from .WATS import WATS
+        if isinstance(model, WATS):
+            if getattr(model, "fused_head", False):
+                raise NotImplementedError(why.format("a WATS surrogate without the fused head"))
+            model, wats = model.base_model, model
+        if type(model) is not SparseCompatibleGCN:
+            raise NotImplementedError(why.format("a SparseCompatibleGCN surrogate, bare or under WATS (a calibrator "
+                                                 f"whose head reads neighbours, here {type(model).__name__}, is not "
+                                                 "covered)"))
+        if model.gc1.out_features > 256 or model.gc2.out_features > 256:
+            raise NotImplementedError(why.format("Hd and C of at most 256"))
+        if values is not None and not bool((values == 1).all()):
+            raise NotImplementedError(why.format("an unweighted graph (this one has values other than 1)"))
+        return model, wats
+
+    def _begin(self, features, adj):
+        self._dense = None
+        if torch.is_tensor(adj):
+            self._dense = adj.detach()
+            start = self.surrogate_operator(self._dense)
+        elif isinstance(adj, RowNormalizedAdjacency):
+            start = adj
+        else:
+            raise TypeError("ori_adj must be a dense tensor, a RowNormalizedAdjacency or a FlippedAdjacency")
+        self._start = start
+        self._n = int(start.n)
+        csr = start.csr() if isinstance(start, FlippedAdjacency) else (start.indptr, start.indices, start.values)
+        model, wats = self._model(csr[2])
+        self._csr = csr
+        self.surrogate.eval()
+        x = features.detach().to(start.device)
+        w1 = model.gc1.weight
+        key = (x.data_ptr(), x._version, tuple(x.shape), w1.data_ptr(), w1._version, model.gc1.bias._version,
+               id(start) if self._dense is None else (self._dense.data_ptr(), self._dense._version))
+        if self._z_key != key:
+            with torch.no_grad():
+                x32 = x.to(torch.float32)
+                z = (x32 @ w1.t()).contiguous()
+                h = F.relu(model.gc1(start @ x32)).contiguous()       # the surrogate's own first layer (model.py:47-48)
+                self._cache = (z, h, z.double().sum(0), h.double().sum(0))
+            self._z_key = key
+        self._x = x
+        return model, wats
+
+    def surrogate_operator(self, dense):
+        return RowNormalizedAdjacency.from_dense(dense.to(self.device))
+
+    # -------------------------------------------------------------------------------------------- the scores
+    def _score(self, model, wats, targets, strategy, steps, topk, return_scores=False):
+        """(best_ids (B, topk), best_scores, scores or None) for the targets (a list of ints)"""
+        if strategy not in ('over', 'under'):
+            raise ValueError("strategy must be 'over' or 'under'")
+        for t in targets:
+            if not 0 <= int(t) < self._n:
+                raise ValueError(f"target {t} outside [0, {self._n})")
+        if not 1 <= topk <= iga_max_topk():
+            raise ValueError(f"n_perturbations = {topk} outside [1, {iga_max_topk()}] (wg_iga_max_topk)")
+        z, h, zsum, hsum = self._cache
+        indptr, indices, _ = self._csr
+        tg = torch.tensor([int(t) for t in targets], dtype=torch.int32).to(self.device)
+        b1, W2, b2 = model.gc1.bias.detach(), model.gc2.weight.detach().contiguous(), model.gc2.bias.detach()
+        logits, state = iga_path_logits(self._n, indptr, indices, z, h, zsum, hsum, b1, W2, b2, tg, steps)
+        B, P, C = logits.shape
+        leaf = logits.requires_grad_(True)
+        out = leaf
+        if wats is not None:
+            with torch.no_grad():
+                temps = wats.temperatures()[tg.long()]
+            out = F.log_softmax(leaf / temps.view(B, 1, 1), dim=2)
+        out = out.reshape(B * P, C)
+        loss = _criterion_rows(out, out.argmax(dim=1), strategy)     # each path point's own label (calib_iga.py:212)
+        g = torch.autograd.grad(loss, leaf)[0].contiguous()
+        res = iga_scores(self._n, indptr, indices, z, h, b1, W2, tg, steps, g, state, topk=topk,
+                         return_scores=return_scores)
+        return res if return_scores else res + (None,)
+
+    def calc_calibration_importance_edge(self, features, adj, target_node, strategy, steps=10, verbose=False):
+        """``calib_iga.py:152-235``: the importance of every partner of ``target_node``, a numpy vector ``[n]``."""
+        model, wats = self._begin(features, adj)
+        _, _, scores = self._score(model, wats, [target_node], strategy, steps, 1, return_scores=True)
+        return scores[0].cpu().numpy().astype("float64")
+
+    # -------------------------------------------------------------------------------------------- the attack
+    def attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy, res_gt=None, steps=10,
+               verbose=False, **kwargs):
+        """``calib_iga.py:38-150``."""
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for calibration attacks")
+        if strategy not in ['over', 'under']:
+            raise ValueError("strategy must be 'over' or 'under'")
+        self.__dict__.pop("modified_adj", None)
+        r = self.attack_many(ori_features, ori_adj, [target_node], n_perturbations, strategy, res_gt, steps=steps,
+                             verbose=verbose)[0]
+        self.target_node = target_node
+        self.flips, self.best_flips, self.trace = r["flips"], r["best_flips"], r["trace"]
+        self.modified_op = r["modified_op"]
+        if "modified_adj" in r:
+            self.__dict__["modified_adj"] = r["modified_adj"]
+        kwargs.get("n_perturb", []).append(r["n_perturb"])
+        kwargs.get("best_conf", []).append(r["best_conf"])
+
+    def attack_many(self, features, adj, targets, n_perturbations, strategy, res_gt, steps=10, verbose=False):
+        """``attack`` for several targets of one graph: all of them are scored by one ``wg_iga_scores`` launch.  Returns
+        one dict per target: ``flips``, ``best_flips``, ``n_perturb``, ``best_conf``, ``trace``, ``modified_op``,
+        ``original_label``, ``original_conf`` (and ``modified_adj`` for a dense ``adj``)."""
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for calibration attacks")
+        if strategy not in ['over', 'under']:
+            raise ValueError("strategy must be 'over' or 'under'")
+        targets = [int(t) for t in targets]
+        model, wats = self._begin(features, adj)
+        results = []
+        if n_perturbations < 1:
+            ids = [[] for _ in targets]
+        else:
+            ids = self._score(model, wats, targets, strategy, steps, int(n_perturbations))[0].cpu().tolist()
+        z = self._cache[0]
+        indptr, indices, _ = self._csr
+        temps = None
+        if wats is not None:
+            with torch.no_grad():
+                temps = wats.temperatures()
+        for t, ranking in zip(targets, ids):
+            order = []
+            for j in ranking:                      # the ranking ends at a missing slot or at t itself (its -10)
+                if j < 0 or j == t:
+                    break
+                order.append(int(j))
+            with torch.no_grad():                  # one launch: the start graph, then every prefix of the ranking
+                out = target_logits(self._n, indptr, indices, z, model.gc1.bias.detach(),
+                                    model.gc2.weight.detach().contiguous(), model.gc2.bias.detach(), t,
+                                    [sorted(order[:k]) for k in range(len(order) + 1)])
+                if temps is not None:
+                    out = F.log_softmax(out / temps[t], dim=1)
+                labels = out.argmax(dim=1).cpu().tolist()
+                probs = F.softmax(out, dim=1).cpu()
+            original_label = labels[0]
+            best_confidence = original_confidence = probs[0, original_label].item()
+            if verbose:
+                print(f"[{strategy.upper()}][Node {t}] Starting calibration attack")
+                print(f"Original label: {original_label}, confidence: {original_confidence:.4f}")
+            attack_times, best, flips, trace = 0, [], [], []
+            for k, j in enumerate(order, start=1):
+                new_label = labels[k]
+                new_confidence = probs[k, new_label].item()
+                flips.append(j)
+                trace.append(dict(partner=j, logits=out[k].cpu(), label=new_label, confidence=new_confidence))
+                if new_label != original_label:
+                    if verbose:
+                        print(f"[{strategy.upper()}][Node {t}] Early stop at step {k}: label flipped")
+                    break
+                attack_times += 1
+                if strategy == 'over' and new_confidence >= best_confidence:
+                    best_confidence, best = new_confidence, sorted(order[:k])
+                elif strategy == 'under' and new_confidence <= best_confidence:
+                    best_confidence, best = new_confidence, sorted(order[:k])
+                if verbose:
+                    print(f"[{strategy.upper()}][Node {t}][Step {k}] flipped edge to node {j}")
+                    print(f"Confidence: {original_confidence:.4f} -> {new_confidence:.4f} "
+                          f"(Δ {new_confidence - original_confidence:+.4f})")
+            r = dict(target=t, flips=flips, best_flips=best, n_perturb=attack_times, best_conf=best_confidence,
+                     trace=trace, modified_op=self._start.with_flips([t] * len(best), best),
+                     original_label=original_label, original_conf=original_confidence)
+            if self._dense is not None:
+                dense = self._dense.clone()
+                for j in best:                                       # calib_iga.py:103-109
+                    v = 1 - dense[t, j]
+                    dense[t, j] = v
+                    dense[j, t] = v
+                r["modified_adj"] = dense
+            if verbose:
+                print(f"[{strategy.upper()}][Node {t}] Attack completed")
+                print(f"Perturbations used: {attack_times}/{n_perturbations}")
+            results.append(r)
+        return results

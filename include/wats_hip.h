@@ -933,6 +933,74 @@ int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_
                      int64_t C, int64_t t, int64_t B, const int32_t* cand_ptr,
                      const int32_t* cand_ids, float* out, void* stream);
 
+/* ----------------------------------------------------------------------
+ * The integrated-gradient scores of calib_attack/calib_iga.py on the sparse
+ * path (csrc/iga.hip), for the two-layer base model (src/gnn/model.py:37-53,
+ * eval mode) on a unit (value-free) canonical CSR.  z = x W1^T and
+ * h = relu(A_hat z + b1) are (n, Hd) float32 arguments, zsum / hsum their
+ * float64 column sums [Hd].
+ *
+ * The reference moves row t of the dense adjacency (the whole row, entry
+ * (t, t) included; column t stays) along two paths with lam = k / steps,
+ * k = 0 .. steps (calib_iga.py:185-206): the remove path w = lam a for the j
+ * with an entry, the add path w = 1 - lam (1 - a) for the j without one.  Per
+ * path point, with deg = sum_j w_j (0 -> 1, a constant then: model.py:44):
+ *   p = (sum_j w_j z_j) / deg          h_t' = relu(p + b1)
+ *   q = (sum_{j != t} w_j h_j + w_t h_t') / deg
+ *   out = W2 q + b2
+ * and the sums over all j follow from row t's neighbour sums and zsum / hsum.
+ *
+ * wg_iga_path_logits (replaces the forward passes of calib_iga.py:201-211):
+ * for B targets (int32 [B], duplicates allowed) the logits (B, P, C) float32
+ * of the P = 2 (steps + 1) path points, remove path first, k ascending, and
+ * the float64 state (B, P, 2 Hd + 2): p [Hd], q [Hd], deg (the sum as
+ * summed: 0 for a zero row), w_t.  One workgroup per target; row t is
+ * gathered once, by 256 / W sub-groups (W: Hd rounded up to a power of two)
+ * whose sums are added in sub-group order.  A row of 0 entries gives the zero
+ * row with deg = 1 at every remove point; a full row the all-ones row at every
+ * add point.  1 <= steps <= 4096.
+ *
+ * wg_iga_scores (replaces the backward passes and calib_iga.py:217-233): from
+ * g_logits (B, P, C) float32 = d loss / d logits at every path point, per
+ * (target, path) in float64
+ *   g_q = W2^T g_out    u = g_q / deg    v = (w_t / deg^2) (g_q * [p + b1 > 0])
+ *   c = -(u . q + v . p)                  (0 at a zero row)
+ *   U = sum_k u, V = sum_k v, cbar = sum_k c       (no division by steps + 1:
+ *                                                   :223 takes the mean of a scalar)
+ * then in one pass over j for all B targets (a tile of 64 rows of z and h is
+ * staged once and read by every target; targets are taken 32 at a time)
+ *   s_j = -(U . h_j + V . z_j + cbar) of the remove path if (t, j) is an entry
+ *         (binary search in row t), +(...) of the add path if not;  s_t = -10
+ * summed in float64 as cbar, then U_f h_jf, V_f z_jf for f ascending, rounded
+ * once.  best_ids (B, topk) int32 / best_scores (B, topk): the best topk per
+ * target under wg_flip_select's total order (a NaN above every number, equal
+ * scores and -0 == +0 by the smaller index, a slot past n entries: id -1,
+ * score -inf); s_t takes part.  1 <= topk <= wg_iga_max_topk() (32).
+ * n_workgroups = 0 picks the grid (ceil(n / 64), at most 512), 1 .. 512 force
+ * it; the result does not depend on it.  workspace: wg_iga_scores_workspace
+ * (B, Hd, &bytes), 8-byte aligned, holds the coefficients and the workgroups'
+ * partial lists, merged by a further launch.  Optional outputs (NULL: none):
+ * coeffs (B, 2, 2 Hd + 1) float64 = U, V, cbar per path; scores (B, n).
+ *
+ * Both: float64 sums in an order fixed by the inputs and the launch shape,
+ * outputs rounded once, no float atomics (the same input gives the same
+ * bits); asynchronous, no allocation, capturable; every argument is checked
+ * before any device call, ids on the device in the bounds-checked variant
+ * only.  1 <= Hd, C <= 256; n or nnz above int32: WG_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int wg_iga_max_topk(void);
+int wg_iga_path_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                       int64_t Hd, const float* z, const float* h, const double* zsum,
+                       const double* hsum, const float* b1, const float* W2, const float* b2,
+                       int64_t C, int64_t B, const int32_t* targets, int32_t steps, float* logits,
+                       double* state, void* stream);
+int wg_iga_scores_workspace(int64_t B, int64_t Hd, int64_t* bytes);
+int wg_iga_scores(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, int64_t Hd,
+                  const float* z, const float* h, const float* b1, const float* W2, int64_t C,
+                  int64_t B, const int32_t* targets, int32_t steps, const float* g_logits,
+                  const double* state, int32_t topk, int32_t n_workgroups, void* workspace,
+                  double* coeffs, float* scores, int32_t* best_ids, float* best_scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
