@@ -27,7 +27,10 @@ last propagation of every expert, the top-k gated mixture, softplus and log_soft
 the selected slices, no (N, E, C) tensor of aggregated outputs), Calib_FGA / flip_select / target_logits (the
 reference's calibration attack as a drop-in class on the sparse path: the flip selection in one HIP pass and the
 candidate's logits from the 2-hop ball of the target), Calib_IGA / iga_path_logits / iga_scores (the reference's
-integrated-gradients attack: its path integrals in closed form, all targets scored in one HIP pass over z and h).
+integrated-gradients attack: its path integrals in closed form, all targets scored in one HIP pass over z and h),
+TemperatureScaling / VectorScaling / MatrixScaling / ETS / scaled_log_probs / train_scaling (the node-wise calibrators:
+their row maps fused in HIP, a training epoch -- loss, gradients, Adam, early stopping -- in one launch on a device
+state block).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -105,6 +108,22 @@ from .gets import (  # noqa: F401
     GETSCalibrator,
     calibrate_with_gets,
     gated_sym_norm_head,
+)
+from .scaling import (  # noqa: F401
+    ETS,
+    MS,
+    TS,
+    VS,
+    MatrixScaling,
+    TemperatureScaling,
+    VectorScaling,
+    calibrate_with_matrix_scaling,
+    calibrate_with_temperature_scaling,
+    calibrate_with_vector_scaling,
+    ensemble_weights,
+    ets_label_probs,
+    scaled_log_probs,
+    train_scaling,
 )
 
 __version__ = "0.1.0"

@@ -107,6 +107,18 @@ SIGNATURES = {
     "wg_wats_head_forward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 8 + [c_vp]),
     "wg_wats_head_workspace": (ctypes.c_int, [c_i64, c_i64, c_i32, ctypes.POINTER(c_i64)]),
     "wg_wats_head_backward": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32] + [c_vp] * 15 + [c_vp]),
+    "wg_scale_max_c": (ctypes.c_int, [c_i32]),
+    "wg_scale_chunk_rows": (ctypes.c_int, []),
+    "wg_scale_forward": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64, c_i64] + [c_vp] * 7 + [c_vp]),
+    "wg_scale_backward_workspace": (ctypes.c_int, [c_i32, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_scale_backward": (ctypes.c_int, [c_i32, c_i32, c_i64, c_i64, c_i64] + [c_vp] * 13 + [c_vp]),
+    "wg_scale_state_bytes": (ctypes.c_int, [c_i32, c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_scale_state_init": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i32, c_f64, c_f64, c_f64, c_vp,
+                                           c_vp]),
+    "wg_scale_state_read": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "wg_scale_epoch": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32,
+                                      c_vp]),
+    "wg_ets_label_probs": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_vp] * 6 + [c_vp]),
     "wg_csr_transpose_map": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wg_bfs_levels": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "wg_gat_long_row": (ctypes.c_int, []),

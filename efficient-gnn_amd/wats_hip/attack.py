@@ -258,13 +258,17 @@ class Calib_FGA(torch.nn.Module):
         self._local = self._local_model()
 
     def _local_model(self):
-        """(gcn, wats or None) when ``wg_target_logits`` applies, else None."""
+        """(gcn, calibrator or None) when ``wg_target_logits`` applies, else None.  The calibrator is a WATS or one
+        of the node-wise calibrators of ``scaling.py`` (TS, VS, MS, ETS), whose map is applied to the (B, C) block."""
         if not self.local_eval:
             return None
         model, wats = self.surrogate, None
         from .WATS import WATS
+        from .scaling import _Scaling
         if isinstance(model, WATS) and not getattr(model, "fused_head", False):
             model, wats = model.base_model, model
+        elif isinstance(model, _Scaling):
+            model, wats = model._base, model
         if type(model) is not SparseCompatibleGCN:
             return None
         if model.gc1.out_features > 256 or model.gc2.out_features > 256:
@@ -319,7 +323,9 @@ class Calib_FGA(torch.nn.Module):
             out = target_logits(self._n, self._csr[0], self._csr[1], self._z, model.gc1.bias.detach(),
                                 model.gc2.weight.detach().contiguous(), model.gc2.bias.detach(), self._t,
                                 [sorted(toggles)])
-            if wats is not None:
+            if wats is not None and hasattr(wats, "row_map"):
+                out = wats.row_map(out)
+            elif wats is not None:
                 out = F.log_softmax(out / wats.temperatures()[self._t], dim=1)
             return out
 

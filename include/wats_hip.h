@@ -1001,6 +1001,108 @@ int wg_iga_scores(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* 
                   const double* state, int32_t topk, int32_t n_workgroups, void* workspace,
                   double* coeffs, float* scores, int32_t* best_ids, float* best_scores, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the four node-wise calibrators (reference calibration/TS.py,
+ * VS.py, MS.py, ETS.py).  Each is a row-wise map of the base model's logits
+ * z (n_total, C) float32, row-major.  mode: 0 TS, 1 VS, 2 MS, 3 ETS.  The
+ * parameters p0 .. p3 are device float32 arrays (unused ones NULL):
+ *   TS   p0 temperature (1)     s = log(exp(temperature) + 1.1)
+ *        out = log_softmax(z * s)                          (TS.py:26, :39-43)
+ *   VS   p0 temperature (C)     the same, s_c per column   (VS.py:33, :45-49)
+ *   MS   p0 W (C, C), p1 b (C)  z' = z - z[:, C - 1],  out = z' W + b, raw
+ *        (MS.py:43-57); flags bit 0 ("normalize"): out = log_softmax(z' W + b)
+ *   ETS  p0 tau (1), p1 w1, p2 w2, p3 w3 (1 each)   temp = log(exp(tau) + 1.1)
+ *        out = log(w1 softmax(z / temp) + w2 softmax(z) + w3 / C)
+ *                                                          (ETS.py:22-26)
+ * rows: an int32 list of n_rows row ids in [0, n_total), any order, repeats
+ * allowed; NULL means all rows (then n_rows == n_total).  Outputs and g_out
+ * are compact: (n_rows, C), entry r belongs to row rows[r].
+ *
+ * wg_scale_forward writes out.  wg_scale_backward replaces autograd's
+ * backward of the same lines: from g_out = d loss / d out it writes g_logits
+ * (nullable; MS's column shift and ETS's mixture included) and, for every
+ * non-NULL g_p0 .. g_p3, the gradient of the matching parameter (ETS: tau,
+ * w1, w2, w3), which needs workspace of wg_scale_backward_workspace bytes
+ * (8-byte aligned).
+ *
+ * wg_scale_epoch is one epoch of calib_train (TS.py:59-83, VS.py:65-89,
+ * MS.py:64-89; modes 0 .. 2) in one launch over the listed rows, labels
+ * int64 (n_total) read at the listed ids: the forward, loss =
+ * -mean(out[r, y_r]) (MS: + Lambda sum |W - I|, gradient Lambda sign(W - I)
+ * with sign(0) = 0), every parameter gradient and the count of rows whose
+ * first maximal column is the label.  Rows are cut into fixed chunks of
+ * wg_scale_chunk_rows() (256) listed rows; each leaves one float64 partial
+ * vector.  The workgroup that arrives last (one relaxed agent-scope
+ * fetch_add per workgroup after its partials are drained; no workgroup waits
+ * on another) adds the partials in chunk order, takes torch's Adam step (lr,
+ * L2 weight decay g += wd * theta, betas 0.9 / 0.999, eps 1e-8,
+ * bias-corrected), updates best_loss and the patience counter as TS.py:75-83
+ * (a NaN loss counts down), and appends the loss and the accuracy to the
+ * traces.  n_workgroups = 0 picks the grid (one workgroup per chunk, at most
+ * 1024), 1 .. 1024 force it; the state's bits do not depend on it.  The
+ * state is one device block of wg_scale_state_bytes bytes, 8-byte aligned:
+ * float64 master parameters and Adam moments, the step count, best_loss, the
+ * patience counter, the stopped flag (1: patience ran out, 2: max_epochs
+ * reached), the epochs run, both traces and the chunk partials.  A launch
+ * that finds stopped set returns without touching anything, so max_epochs
+ * launches may be enqueued back to back.  mode, flags, C, max_epochs and
+ * max_rows of every wg_scale_epoch must be those the block was initialised
+ * with (n_rows <= max_rows is checked on the host, the rest on the device in
+ * the bounds-checked variant).  wg_scale_state_init fills it
+ * (init_params NULL: the reference's ones; else n float32 in state order, MS:
+ * W then b); wg_scale_state_read copies the float32-rounded parameters out
+ * (params, nullable) and info (nullable) float64 [5 + 2 max_epochs]:
+ * stopped, epochs run, Adam steps, patience left, best loss, then the loss
+ * trace and the accuracy trace.
+ *
+ * wg_ets_label_probs: the one pass ETS.fit needs (ETS.py:50-76): p0y[r] =
+ * softmax(z / tau)[y] and p1y[r] = softmax(z)[y] of row rows[r], float64,
+ * with the RAW tau as the divisor (ETS.py:43, :57).  A label outside [0, C)
+ * gives NaN.
+ *
+ * Arithmetic: a wave per row; the scaled logits, the row maximum, the sum of
+ * exp, the log and every gradient are float64; out, g_logits and
+ * wg_scale_backward's parameter gradients are rounded to float32 once; every
+ * sum's order is fixed by the rows and C; no float atomics: the same input
+ * gives the same bits.  A NaN in a row stays in that row's out / g_logits
+ * (and reaches the loss and the parameter gradients).
+ *
+ * wg_scale_max_c(mode): 256 for TS, VS and ETS (four columns per lane); 64
+ * for MS, where a lane owns one column and keeps that column of dW in 64
+ * float64 registers (128 VGPRs) while W sits in LDS (33 KB, shared with the
+ * workgroup's reduction buffer).  Checked before any device call: a bad
+ * mode, a negative size, C < 1, a NULL pointer not named nullable, rows NULL
+ * with n_rows != n_total, an output that aliases an input: WG_ERR_INVALID; C
+ * above the limit, sizes above int32: WG_ERR_UNSUPPORTED.  Row ids, labels
+ * and the state's header are checked on the device in the bounds-checked
+ * variant only.  n_rows == 0 is WG_OK with no launch (wg_scale_epoch:
+ * WG_ERR_INVALID).  Asynchronous, allocate nothing.
+ * ---------------------------------------------------------------------- */
+int wg_scale_max_c(int32_t mode);
+int wg_scale_chunk_rows(void);
+int wg_scale_forward(int32_t mode, int32_t flags, int64_t n_total, int64_t n_rows, int64_t C,
+                     const float* logits, const int32_t* rows, const float* p0, const float* p1,
+                     const float* p2, const float* p3, float* out, void* stream);
+int wg_scale_backward_workspace(int32_t mode, int64_t n_rows, int64_t C, int64_t* bytes);
+int wg_scale_backward(int32_t mode, int32_t flags, int64_t n_total, int64_t n_rows, int64_t C,
+                      const float* logits, const int32_t* rows, const float* p0, const float* p1,
+                      const float* p2, const float* p3, const float* g_out, float* g_logits,
+                      float* g_p0, float* g_p1, float* g_p2, float* g_p3, void* workspace,
+                      void* stream);
+int wg_scale_state_bytes(int32_t mode, int64_t C, int64_t max_epochs, int64_t max_rows,
+                         int64_t* bytes);
+int wg_scale_state_init(void* state, int32_t mode, int32_t flags, int64_t C, int64_t max_epochs,
+                        int64_t max_rows, int32_t patience, double lr, double weight_decay,
+                        double lambda, const float* init_params, void* stream);
+int wg_scale_state_read(const void* state, int32_t mode, int64_t C, int64_t max_epochs,
+                        float* params, double* info, void* stream);
+int wg_scale_epoch(void* state, int32_t mode, int32_t flags, int64_t C, int64_t max_epochs,
+                   int64_t max_rows, int64_t n_total, int64_t n_rows, const float* logits,
+                   const int32_t* rows, const int64_t* labels, int32_t n_workgroups, void* stream);
+int wg_ets_label_probs(int64_t n_total, int64_t n_rows, int64_t C, const float* logits,
+                       const int32_t* rows, const int64_t* labels, const float* temperature,
+                       double* p0y, double* p1y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
