@@ -8,7 +8,10 @@
 //                          the same tensors (contraction off: no fused multiply-add)
 //   flip_merge_kernel      the workgroups' partial lists merged by one workgroup (a second launch)
 //   target_logits_kernel   the logits of node t under B candidate adjacencies, one workgroup per candidate,
-//                          from the 2-hop ball of t alone: float64 sums in a fixed order, rounded once
+//                          from the 2-hop ball of t alone: float64 sums in a fixed order, rounded once.  The same
+//                          kernel evaluates the trials of the random attacks (calib_random.py:127-186,
+//                          calib_rnd.py:169-236): a target per candidate, t itself among the partners (its self
+//                          loop), and deltas of the target's own feature row carried as dz = W1 delta
 //
 // Ranking is a total order on (score, index) -- a NaN above every number, equal scores by smaller index,
 // -0 == +0 -- packed into one 64-bit key whose maximum is the winner, so the result cannot depend on how
@@ -205,6 +208,13 @@ struct LogitArgs {
   const int32_t* cand_ptr = nullptr;
   const int32_t* cand_ids = nullptr;
   float* out = nullptr;        // (B, C)
+  // the trials (wg_trial_logits); all NULL for wg_target_logits
+  const int32_t* trial_t = nullptr;     // [B]: candidate b's own target, which may be among its partners
+  int64_t nfeat = 0;
+  const float* W1 = nullptr;            // (Hd, nfeat)
+  const int32_t* feat_ptr = nullptr;    // [B + 1]; NULL: no feature deltas
+  const int32_t* feat_ids = nullptr;
+  const float* feat_delta = nullptr;
 };
 
 __device__ inline bool contains(const int32_t* __restrict__ a, int64_t len, int32_t key) {
@@ -215,6 +225,7 @@ __device__ inline bool contains(const int32_t* __restrict__ a, int64_t len, int3
 // one j of N'(t): its row under the toggle set T (the partners whose entry in row j differs from the base)
 struct Item {
   bool live = false;
+  bool has_t = false;   // t is in N'(j): the row gathers z_t, so it carries dz (read with feature deltas only)
   int64_t j = 0, s = 0, len = 0, deg = 0;
   const int32_t* T = nullptr;
   int nT = 0;
@@ -280,6 +291,7 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
   constexpr int kSubWave = 64 / W;   // sub-groups per wave
   __shared__ double red[kWaves][W][4];
   __shared__ double y2[256];
+  __shared__ double dz_sh[256];
   __shared__ int32_t t_sh;
   __shared__ int inter_sh, long_sh;
   __shared__ int32_t long_list[kLongList];
@@ -289,13 +301,33 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
   WG_DCHECK(c0 >= 0 && c0 <= c1, "target logits: candidate %d is [%d, %d)", (int)blockIdx.x, (int)c0, (int)c1);
   const int32_t* S = a.cand_ids + c0;
   const int nS = c1 - c0;
-  const int64_t st = a.indptr[a.t], lt = a.indptr[a.t + 1] - st;
+  const bool trial = a.trial_t != nullptr;
+  const int64_t t = trial ? (int64_t)a.trial_t[blockIdx.x] : a.t;
+  WG_DCHECK(t >= 0 && t < a.n, "target logits: candidate %d target %lld outside [0, %lld)", (int)blockIdx.x, (long long)t,
+            (long long)a.n);
+  const int64_t st = a.indptr[t], lt = a.indptr[t + 1] - st;
   const int32_t* Nt = a.indices + st;
-  if (threadIdx.x == 0) t_sh = (int32_t)a.t, inter_sh = 0, long_sh = 0;
+  if (threadIdx.x == 0) t_sh = (int32_t)t, inter_sh = 0, long_sh = 0;
+  // dz = W1 delta of the target's own feature row: one thread per hidden unit, the features in ascending order
+  const bool feat = a.feat_ptr != nullptr;
+  if (feat && (int64_t)threadIdx.x < a.Hd) {
+    const int32_t f0 = a.feat_ptr[blockIdx.x], f1 = a.feat_ptr[blockIdx.x + 1];
+    WG_DCHECK(f0 >= 0 && f0 <= f1, "trial logits: trial %d features are [%d, %d)", (int)blockIdx.x, (int)f0, (int)f1);
+    const float* w = a.W1 + (int64_t)threadIdx.x * a.nfeat;
+    double d = 0.0;
+    for (int32_t q = f0; q < f1; ++q) {
+      const int32_t f = a.feat_ids[q];
+      WG_DCHECK(f >= 0 && f < a.nfeat && (q == f0 || a.feat_ids[q - 1] < f),
+                "trial logits: trial %d feature %d is outside [0, %lld) or not ascending", (int)blockIdx.x, (int)f,
+                (long long)a.nfeat);
+      d += (double)a.feat_delta[q] * (double)w[f];
+    }
+    dz_sh[threadIdx.x] = d;
+  }
   __syncthreads();
   int hits = 0;
   for (int q = threadIdx.x; q < nS; q += kBlock) {
-    WG_DCHECK(S[q] >= 0 && S[q] < a.n && S[q] != a.t && (q == 0 || S[q - 1] < S[q]),
+    WG_DCHECK(S[q] >= 0 && S[q] < a.n && (trial || S[q] != t) && (q == 0 || S[q - 1] < S[q]),
               "target logits: candidate %d partner %d is outside [0, %lld), the target or not ascending", (int)blockIdx.x,
               (int)S[q], (long long)a.n);
     hits += contains(Nt, lt, S[q]) ? 1 : 0;
@@ -320,13 +352,18 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
   double bias[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) bias[c] = (double)a.b1[VEC ? std::min<int64_t>(4 * fo[0] + c, a.Hd - 1) : fo[c]];
+  double dz[4] = {0.0, 0.0, 0.0, 0.0};
+  if (feat) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dz[c] = dz_sh[VEC ? std::min<int64_t>(4 * fo[0] + c, a.Hd - 1) : fo[c]];
+  }
 
   // item i: the base row's entries, then the candidate's partners; dead when the toggle removes it
   auto item = [&](int64_t i) {
     Item it;
     if (i < lt) {
       it.j = Nt[i];
-      WG_DCHECK(it.j >= 0 && it.j < a.n, "target logits: row %lld column %lld outside [0, %lld)", (long long)a.t,
+      WG_DCHECK(it.j >= 0 && it.j < a.n, "target logits: row %lld column %lld outside [0, %lld)", (long long)t,
                 (long long)it.j, (long long)a.n);
       it.live = !contains(S, nS, (int32_t)it.j);
     } else {
@@ -335,22 +372,26 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
     }
     it.s = a.indptr[it.j];
     it.len = a.indptr[it.j + 1] - it.s;
-    if (it.j == a.t) {
+    if (it.j == t) {
       it.T = S, it.nT = nS, it.deg = deg_t;
+      it.has_t = true;           // a live item j == t: the self loop is in N'(t)
     } else if (i >= lt) {
+      const bool in_base = contains(a.indices + it.s, it.len, (int32_t)t);
       it.T = &t_sh, it.nT = 1;
-      it.deg = it.len + 1 - 2 * (contains(a.indices + it.s, it.len, (int32_t)a.t) ? 1 : 0);
+      it.deg = it.len + 1 - 2 * (in_base ? 1 : 0);
+      it.has_t = !in_base;
     } else {
       it.deg = it.len;
+      if (feat) it.has_t = contains(a.indices + it.s, it.len, (int32_t)t);   // asked of the row: no symmetry assumed
     }
     return it;
   };
   // h_j = max(y1_j + b1, 0) of the finished row sum, added to hs
-  auto add_h = [&](const double* sum, int64_t deg, double* hs) {
+  auto add_h = [&](const double* sum, int64_t deg, bool with_dz, double* hs) {
     const double inv = 1.0 / (double)(deg > 0 ? deg : 1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const double h = inv * sum[c] + bias[c];
+      const double h = inv * (with_dz ? sum[c] + dz[c] : sum[c]) + bias[c];
       hs[c] += h > 0.0 ? h : 0.0;
     }
   };
@@ -375,7 +416,7 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[c] += __shfl_down(acc[c], off, 64);
     }
-    add_h(acc, it.deg, hs);   // meaningful in the lanes below W
+    add_h(acc, it.deg, feat && it.has_t, hs);   // meaningful in the lanes below W
   }
   __syncthreads();
   // long rows in ascending item order: the whole workgroup per row, the waves' sums in wave order, h into wave
@@ -413,7 +454,7 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
 #pragma unroll
           for (int w = 1; w < kWaves; ++w) tot[c] += red[w][sub][c];
         }
-        add_h(tot, it.deg, hs);
+        add_h(tot, it.deg, feat && it.has_t, hs);
       }
       __syncthreads();   // red is written again by the next long row
     }
@@ -447,36 +488,30 @@ __global__ __launch_bounds__(kBlock) void target_logits_kernel(LogitArgs a) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-}  // namespace
-}  // namespace wg
-
-using namespace wg;
-
-extern "C" {
-
-int wg_target_long_row(void) { return kLongRow; }
-
-int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, int64_t Hd, const float* z,
-                     const float* b1, const float* W2, const float* b2, int64_t C, int64_t t, int64_t B,
-                     const int32_t* cand_ptr, const int32_t* cand_ids, float* out, void* stream_) {
-  if (n < 1 || nnz < 0) return fail(WG_ERR_INVALID, "wg_target_logits: n=%lld nnz=%lld", (long long)n, (long long)nnz);
+// what wg_target_logits and wg_trial_logits check alike, before any device call
+int check_sizes(const char* who, int64_t n, int64_t nnz, int64_t Hd, int64_t C, int64_t B) {
+  if (n < 1 || nnz < 0) return fail(WG_ERR_INVALID, "%s: n=%lld nnz=%lld", who, (long long)n, (long long)nnz);
   if (n > INT32_MAX || nnz > INT32_MAX)
-    return fail(WG_ERR_UNSUPPORTED, "wg_target_logits: n=%lld or nnz=%lld exceeds int32", (long long)n, (long long)nnz);
+    return fail(WG_ERR_UNSUPPORTED, "%s: n=%lld or nnz=%lld exceeds int32", who, (long long)n, (long long)nnz);
   if (Hd < 1 || C < 1 || B < 1)
-    return fail(WG_ERR_INVALID, "wg_target_logits: Hd=%lld C=%lld B=%lld must be >= 1", (long long)Hd, (long long)C, (long long)B);
-  if (Hd > 256 || C > 256)
-    return fail(WG_ERR_UNSUPPORTED, "wg_target_logits: Hd=%lld or C=%lld above 256", (long long)Hd, (long long)C);
-  if (B > INT32_MAX) return fail(WG_ERR_UNSUPPORTED, "wg_target_logits: B=%lld exceeds int32", (long long)B);
-  if (t < 0 || t >= n) return fail(WG_ERR_INVALID, "wg_target_logits: target %lld outside [0, %lld)", (long long)t, (long long)n);
+    return fail(WG_ERR_INVALID, "%s: Hd=%lld C=%lld B=%lld must be >= 1", who, (long long)Hd, (long long)C, (long long)B);
+  if (Hd > 256 || C > 256) return fail(WG_ERR_UNSUPPORTED, "%s: Hd=%lld or C=%lld above 256", who, (long long)Hd, (long long)C);
+  if (B > INT32_MAX) return fail(WG_ERR_UNSUPPORTED, "%s: B=%lld exceeds int32", who, (long long)B);
+  return WG_OK;
+}
+
+int check_pointers(const char* who, int64_t nnz, const int64_t* indptr, const int32_t* indices, const float* z,
+                   const float* b1, const float* W2, const float* b2, const int32_t* cand_ptr, const float* out) {
   if (!indptr || !z || !b1 || !W2 || !b2 || !cand_ptr || !out)
-    return fail(WG_ERR_INVALID, "wg_target_logits: NULL indptr / z / b1 / W2 / b2 / cand_ptr / out");
-  if (nnz > 0 && !indices) return fail(WG_ERR_INVALID, "wg_target_logits: NULL indices with nnz=%lld", (long long)nnz);
-  LogitArgs a;
-  a.n = n, a.Hd = Hd, a.C = C, a.t = t, a.indptr = indptr, a.indices = indices, a.z = z, a.b1 = b1, a.W2 = W2, a.b2 = b2;
-  a.cand_ptr = cand_ptr, a.cand_ids = cand_ids, a.out = out;
+    return fail(WG_ERR_INVALID, "%s: NULL indptr / z / b1 / W2 / b2 / cand_ptr / out", who);
+  if (nnz > 0 && !indices) return fail(WG_ERR_INVALID, "%s: NULL indices with nnz=%lld", who, (long long)nnz);
+  return WG_OK;
+}
+
+int launch_logits(const LogitArgs& a, int64_t B, void* stream_) {
   int W = 1;
-  while (W < 64 && W < ceil_div(Hd, 4)) W <<= 1;
-  const bool vec = (Hd % 4 == 0) && aligned16(z);
+  while (W < 64 && W < ceil_div(a.Hd, 4)) W <<= 1;
+  const bool vec = (a.Hd % 4 == 0) && aligned16(a.z);
   const dim3 grid((unsigned)B), block(kBlock);
   hipStream_t stream = as_stream(stream_);
 #define WG_TARGET_CASE(w)                                                                     \
@@ -496,6 +531,48 @@ int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_
 #undef WG_TARGET_CASE
   WG_LAUNCH_CHECK();
   return WG_OK;
+}
+
+}  // namespace
+}  // namespace wg
+
+using namespace wg;
+
+extern "C" {
+
+int wg_target_long_row(void) { return kLongRow; }
+
+int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, int64_t Hd, const float* z,
+                     const float* b1, const float* W2, const float* b2, int64_t C, int64_t t, int64_t B,
+                     const int32_t* cand_ptr, const int32_t* cand_ids, float* out, void* stream_) {
+  if (const int rc = check_sizes("wg_target_logits", n, nnz, Hd, C, B)) return rc;
+  if (t < 0 || t >= n) return fail(WG_ERR_INVALID, "wg_target_logits: target %lld outside [0, %lld)", (long long)t, (long long)n);
+  if (const int rc = check_pointers("wg_target_logits", nnz, indptr, indices, z, b1, W2, b2, cand_ptr, out)) return rc;
+  LogitArgs a;
+  a.n = n, a.Hd = Hd, a.C = C, a.t = t, a.indptr = indptr, a.indices = indices, a.z = z, a.b1 = b1, a.W2 = W2, a.b2 = b2;
+  a.cand_ptr = cand_ptr, a.cand_ids = cand_ids, a.out = out;
+  return launch_logits(a, B, stream_);
+}
+
+int wg_trial_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, int64_t Hd, const float* z,
+                    const float* b1, const float* W2, const float* b2, int64_t C, int64_t B, const int32_t* trial_t,
+                    const int32_t* cand_ptr, const int32_t* cand_ids, int64_t nfeat, const float* W1,
+                    const int32_t* feat_ptr, const int32_t* feat_ids, const float* feat_delta, float* out, void* stream_) {
+  if (const int rc = check_sizes("wg_trial_logits", n, nnz, Hd, C, B)) return rc;
+  if (const int rc = check_pointers("wg_trial_logits", nnz, indptr, indices, z, b1, W2, b2, cand_ptr, out)) return rc;
+  if (!trial_t) return fail(WG_ERR_INVALID, "wg_trial_logits: NULL trial_t");
+  if (feat_ptr) {
+    if (nfeat < 1) return fail(WG_ERR_INVALID, "wg_trial_logits: nfeat=%lld with feature deltas", (long long)nfeat);
+    if (nfeat > INT32_MAX) return fail(WG_ERR_UNSUPPORTED, "wg_trial_logits: nfeat=%lld exceeds int32", (long long)nfeat);
+    if (!W1) return fail(WG_ERR_INVALID, "wg_trial_logits: NULL W1 with feature deltas");
+    if ((feat_ids == nullptr) != (feat_delta == nullptr))
+      return fail(WG_ERR_INVALID, "wg_trial_logits: feat_ids and feat_delta are both given or both NULL");
+  }
+  LogitArgs a;
+  a.n = n, a.Hd = Hd, a.C = C, a.t = 0, a.indptr = indptr, a.indices = indices, a.z = z, a.b1 = b1, a.W2 = W2, a.b2 = b2;
+  a.cand_ptr = cand_ptr, a.cand_ids = cand_ids, a.out = out, a.trial_t = trial_t;
+  if (feat_ptr) a.nfeat = nfeat, a.W1 = W1, a.feat_ptr = feat_ptr, a.feat_ids = feat_ids, a.feat_delta = feat_delta;
+  return launch_logits(a, B, stream_);
 }
 
 int wg_flip_select_workspace(int64_t* bytes) {

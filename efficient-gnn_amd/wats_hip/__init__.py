@@ -28,6 +28,8 @@ the selected slices, no (N, E, C) tensor of aggregated outputs), Calib_FGA / fli
 reference's calibration attack as a drop-in class on the sparse path: the flip selection in one HIP pass and the
 candidate's logits from the 2-hop ball of the target), Calib_IGA / iga_path_logits / iga_scores (the reference's
 integrated-gradients attack: its path integrals in closed form, all targets scored in one HIP pass over z and h),
+Calib_Random / Calib_RND / trial_logits (the reference's random baseline attacks: a step's trials drawn ahead from
+the reference's own random stream and evaluated by one HIP launch, several targets in lock step),
 TemperatureScaling / VectorScaling / MatrixScaling / ETS / scaled_log_probs / train_scaling (the node-wise calibrators:
 their row maps fused in HIP, a training epoch -- loss, gradients, Adam, early stopping -- in one launch on a device
 state block).
@@ -63,6 +65,8 @@ from .flips import FlippedAdjacency  # noqa: F401
 from .attack import (  # noqa: F401
     Calib_FGA,
     Calib_IGA,
+    Calib_Random,
+    Calib_RND,
     flip_select,
     iga_path_logits,
     iga_scores,
@@ -70,6 +74,7 @@ from .attack import (  # noqa: F401
     kl_divergence_with_uniform,
     overconfidence_objective,
     target_logits,
+    trial_logits,
     underconfidence_objective,
 )
 from .gats import (  # noqa: F401

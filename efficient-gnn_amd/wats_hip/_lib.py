@@ -95,6 +95,8 @@ SIGNATURES = {
     "wg_target_long_row": (ctypes.c_int, []),
     "wg_target_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                         c_vp, c_vp, c_vp, c_vp]),
+    "wg_trial_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
+                                       c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wg_iga_max_topk": (ctypes.c_int, []),
     "wg_iga_path_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_i64, c_i64, c_vp, c_i32, c_vp,
                                                                                         c_vp, c_vp]),

@@ -24,6 +24,10 @@ Results: ``flips`` (the partners in the order flipped), ``best_flips`` (the togg
 confidence, ascending), ``modified_op`` (that adjacency as a view: ``.materialize()`` / ``.to_graph()``),
 ``modified_adj`` (a dense tensor when ``ori_adj`` was dense; otherwise ``AttributeError``), ``trace`` (one dict per
 evaluated candidate: partner, logits row, label, confidence).
+
+Further down: ``Calib_IGA`` (``calib_attack/calib_iga.py``) and the random baselines ``Calib_Random`` / ``Calib_RND``
+(``calib_attack/calib_random.py``, ``calib_rnd.py``; DESIGN.md 4.3 "Random trials") with ``trial_logits``
+(``wg_trial_logits``: all trials of a step in one launch).
 """
 from __future__ import annotations
 
@@ -870,3 +874,528 @@ class Calib_IGA(torch.nn.Module):
                 print(f"Perturbations used: {attack_times}/{n_perturbations}")
             results.append(r)
         return results
+
+
+# ------------------------------------------------------------------------------------------------ the random attacks
+def trial_logits(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.Tensor, b1: torch.Tensor,
+                 W2: torch.Tensor, b2: torch.Tensor, trials, W1: torch.Tensor | None = None) -> torch.Tensor:
+    """``wg_trial_logits``: the ``(B, C)`` logits of B trials of the random attacks in one launch.  ``trials`` is a
+    list of ``(t, partners, {feature: delta})`` (partners ascending and distinct, ``t`` itself allowed: its self loop;
+    the dict may be empty or None), or prebuilt int32 / float32 device arrays that the caller checked:
+    ``(trial_t, cand_ptr, cand_ids)`` or ``(trial_t, cand_ptr, cand_ids, feat_ptr, feat_ids, feat_delta)``.
+    ``z = x @ W1.T``; ``W1 (Hd, nfeat)`` is read only with feature deltas."""
+    device = require_gpu(z.device if z.is_cuda else None)
+    Hd, C = int(z.shape[1]), int(W2.shape[0])
+    if z.shape[0] != n or W2.shape[1] != Hd or b1.numel() != Hd or b2.numel() != C:
+        raise ValueError("trial_logits: z (n, Hd), b1 [Hd], W2 (C, Hd), b2 [C] expected")
+    feat_ptr = feat_ids = feat_delta = None
+    if isinstance(trials, tuple):
+        trial_t, cand_ptr, cand_ids = trials[:3]
+        if len(trials) == 6:
+            feat_ptr, feat_ids, feat_delta = trials[3:]
+    else:
+        nfeat = None if W1 is None else int(W1.shape[1])
+        ts, ptrs, ids, fptrs, fids, fdel = [], [0], [], [0], [], []
+        for t, S, feats in trials:
+            t, S = int(t), [int(j) for j in S]
+            if not 0 <= t < n:
+                raise ValueError(f"a trial's target {t} is outside [0, {n})")
+            if any(b <= a for a, b in zip(S, S[1:])) or any(not 0 <= j < n for j in S):
+                raise ValueError("a trial's partners must be ascending, distinct and inside [0, n)")
+            ts.append(t)
+            ids += S
+            ptrs.append(len(ids))
+            for f in sorted(feats or ()):
+                if nfeat is None or not 0 <= int(f) < nfeat:
+                    raise ValueError("a trial's features need W1 (Hd, nfeat) and ids inside [0, nfeat)")
+                fids.append(int(f))
+                fdel.append(float(feats[f]))
+            fptrs.append(len(fids))
+        packed = dict(t=torch.tensor(ts, dtype=torch.int32), ptr=torch.tensor(ptrs, dtype=torch.int32),
+                      ids=torch.tensor(ids, dtype=torch.int32))
+        if fids:
+            packed.update(fptr=torch.tensor(fptrs, dtype=torch.int32), fids=torch.tensor(fids, dtype=torch.int32),
+                          fdel=torch.tensor(fdel, dtype=torch.float32))
+        from .flips import _upload
+        d = _upload(device, packed)                              # one copy
+        trial_t, cand_ptr, cand_ids = d["t"], d["ptr"], d["ids"]
+        if fids:
+            feat_ptr, feat_ids, feat_delta = d["fptr"], d["fids"], d["fdel"]
+    B = int(trial_t.numel())
+    if int(cand_ptr.numel()) != B + 1 or (feat_ptr is not None and int(feat_ptr.numel()) != B + 1):
+        raise ValueError("trial_logits: cand_ptr / feat_ptr need B + 1 entries")
+    nfeat = 0
+    if feat_ptr is not None:
+        if W1 is None or W1.dim() != 2 or W1.shape[0] != Hd:
+            raise ValueError("trial_logits: feature deltas need W1 (Hd, nfeat)")
+        W1 = W1.detach().to(device, torch.float32).contiguous()
+        nfeat = int(W1.shape[1])
+    out = torch.empty((B, C), dtype=torch.float32, device=device)
+    nnz = int(indices.numel())
+    opt = lambda v: ptr(v) if v is not None and v.numel() else None
+    with torch.cuda.device(device):
+        check(_lib.load().wg_trial_logits(n, nnz, ptr(indptr), opt(indices), Hd, ptr(z), ptr(b1), ptr(W2), ptr(b2), C,
+                                          B, ptr(trial_t), ptr(cand_ptr), opt(cand_ids), nfeat,
+                                          ptr(W1) if feat_ptr is not None else None,
+                                          ptr(feat_ptr) if feat_ptr is not None else None, opt(feat_ids),
+                                          opt(feat_delta), ptr(out), stream_handle(device)), "trial_logits")
+    return out
+
+
+def _nth_absent(occupied, idx):
+    """The ``idx``-th id (from 0) that is not in the ascending list ``occupied``."""
+    j = idx
+    for e in occupied:
+        if e <= j:
+            j += 1
+        else:
+            break
+    return j
+
+
+class _Target:
+    """One target's state: the accepted toggles and feature row, its random stream and what it has recorded."""
+
+    def __init__(self, t, rng, base_row, x_row):
+        self.t, self.rng = t, rng
+        self.base_row = base_row                   # row t of the start CSR: ascending host ints
+        self.toggles = set()                       # partners whose entry differs from the start adjacency
+        self.x0 = x_row                            # host float32 copies of row t of the features
+        self.x = x_row.copy()
+        self.changed = {}                          # feature -> current - original, where it is not 0
+        self.flips, self.feature_flips, self.trace = [], {}, []
+        self.attack_times = 0
+        self.label = self.best_conf = self.conf0 = None
+
+    def present(self):
+        return sorted(set(self.base_row).symmetric_difference(self.toggles))
+
+
+class _RandomAttack(torch.nn.Module):
+    """What ``Calib_Random`` and ``Calib_RND`` share (their loops are the same draws in the same order: ``randint(0,
+    k - 1)`` and ``choice`` of a k-list both take one ``_randbelow(k)``)."""
+
+    _default_strategy = "under"
+    _name = "CALIB_RANDOM"
+
+    def __init__(self, model, attack_structure=True, attack_features=False, device=None, *, local_eval: bool = True):
+        super().__init__()
+        assert attack_features or attack_structure, 'attack_features or attack_structure cannot be both False'
+        self.surrogate = model
+        self.attack_structure, self.attack_features = bool(attack_structure), bool(attack_features)
+        self.device = require_gpu(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.local_eval = bool(local_eval)
+        self.modified_features = None
+        self.modified_op = None
+        self.target_node = None
+        self.flips, self.best_flips, self.feature_flips, self.trace = [], [], {}, []
+        self._z_key = self._z = None
+
+    def __getattr__(self, name):
+        if name == "modified_adj":
+            raise AttributeError("modified_adj exists only when ori_adj was dense (Calib_RND: or scipy); read "
+                                 "modified_op (.materialize() gives an operator, .to_graph() a CSR)")
+        return super().__getattr__(name)
+
+    # -------------------------------------------------------------------------------------------- inputs
+    def _operator(self, ori_adj):
+        """(start operator, the dense tensor it came from or None)"""
+        if torch.is_tensor(ori_adj):
+            dense = ori_adj.detach()
+            return RowNormalizedAdjacency.from_dense(dense.to(self.device).float()), dense
+        if isinstance(ori_adj, RowNormalizedAdjacency):
+            return ori_adj, None
+        raise TypeError("ori_adj must be a dense tensor, a RowNormalizedAdjacency or a FlippedAdjacency")
+
+    def _features(self, ori_features):
+        return ori_features
+
+    def _begin(self, ori_features, ori_adj):
+        self.__dict__.pop("modified_adj", None)
+        start, self._dense = self._operator(ori_adj)
+        self._start, self._n = start, int(start.n)
+        self._x_in = self._features(ori_features)
+        self._x = self._x_in.detach().to(start.device)
+        self._nfeat = int(self._x.shape[1])
+        self._csr = start.csr() if isinstance(start, FlippedAdjacency) else (start.indptr, start.indices, start.values)
+        self.surrogate.eval()
+        self._local = self._local_model()
+        self._x_trial = None                       # the view path's clone of x, made once per attack
+
+    def _local_model(self):
+        """(gcn, calibrator or None) when ``wg_trial_logits`` applies (as ``Calib_FGA._local_model``); feature trials
+        only for the bare model and the node-wise calibrators of ``scaling.py``."""
+        got = Calib_FGA._local_model(self)
+        if got is not None and self.attack_features and got[1] is not None and not hasattr(got[1], "row_map"):
+            return None
+        return got
+
+    def _new_target(self, t, rng):
+        t = int(t)
+        if not 0 <= t < self._n:
+            raise ValueError(f"target {t} outside [0, {self._n})")
+        indptr, indices, _ = self._csr
+        s, e = (int(v) for v in indptr[t:t + 2].cpu())
+        return _Target(t, rng, indices[s:e].cpu().tolist(), self._x[t].to(torch.float32).cpu().numpy().copy())
+
+    # -------------------------------------------------------------------------------------------- one trial
+    def _draw(self, T, present, occupied):
+        """The draws of one trial (``calib_random.py:133-149``, ``:354-393``, ``:413-424``): ("edge", add, j),
+        ("feature", add, f, new value) or None when nothing can be perturbed."""
+        rng = T.rng
+        if self.attack_structure and self.attack_features:
+            structure = rng.choice([True, False])
+        else:
+            structure = self.attack_structure
+        if structure:
+            n_absent = self._n - len(occupied)
+            if not (n_absent or present):
+                return None
+            if n_absent and present:
+                add = rng.choice([True, False])
+            else:
+                add = bool(n_absent)
+            if add:
+                return "edge", True, _nth_absent(occupied, rng.randint(0, n_absent - 1))
+            return "edge", False, present[rng.randint(0, len(present) - 1)]
+        if self._nfeat == 0:
+            return None
+        f = rng.randint(0, self._nfeat - 1)
+        cur = T.x[f]
+        new = type(cur)(1 - cur)
+        return "feature", bool(new > cur), f, new
+
+    def _draw_step(self, T, max_trials):
+        """The ``max_trials`` trials of one step drawn ahead, and what puts the stream back after trial k: the state
+        before the step and the lists the draws were made over (``_rewind`` draws k + 1 trials again, which costs less
+        than a ``getstate`` per trial)."""
+        present = T.present()
+        occupied = sorted(set(present) | {T.t})
+        state = T.rng.getstate()
+        return [self._draw(T, present, occupied) for _ in range(max_trials)], (state, present, occupied)
+
+    def _rewind(self, T, rewind, k):
+        """The random state after trial ``k`` of the step: where the reference stopped drawing."""
+        state, present, occupied = rewind
+        T.rng.setstate(state)
+        for _ in range(k + 1):
+            self._draw(T, present, occupied)
+
+    def _trial_spec(self, T, d):
+        """(partners, {feature: delta}) of the accepted state with the trial applied"""
+        if d[0] == "edge":
+            return sorted(T.toggles.symmetric_difference({d[2]})), T.changed
+        feats = dict(T.changed)
+        delta = float(d[3]) - float(T.x0[d[2]])
+        if delta == 0.0:
+            feats.pop(d[2], None)
+        else:
+            feats[d[2]] = delta
+        return sorted(T.toggles), feats
+
+    def _map(self, out, targets):
+        """The calibrator's row map of a (B, C) block of base logits; ``targets``: each row's node."""
+        wats = self._local[1]
+        if wats is None:
+            return out
+        if hasattr(wats, "row_map"):
+            return wats.row_map(out)
+        temps = wats.temperatures()[torch.tensor(targets, dtype=torch.int64, device=out.device)]
+        return F.log_softmax(out / temps.unsqueeze(1), dim=1)
+
+    def _launch(self, specs):
+        """One ``wg_trial_logits`` launch and one host read: (logits (B, C) on the host, labels, confidences)."""
+        model = self._local[0]
+        w1 = model.gc1.weight
+        key = (self._x.data_ptr(), self._x._version, tuple(self._x.shape), w1.data_ptr(), w1._version)
+        if self._z_key != key:
+            self._z, self._z_key = (self._x.to(torch.float32) @ w1.t()).contiguous(), key
+        with torch.no_grad():
+            out = trial_logits(self._n, self._csr[0], self._csr[1], self._z, model.gc1.bias.detach(),
+                               model.gc2.weight.detach().contiguous(), model.gc2.bias.detach(), specs,
+                               W1=w1.detach() if any(s[2] for s in specs) else None)
+            out = self._map(out, [s[0] for s in specs])
+            return self._read(out)
+
+    @staticmethod
+    def _read(out):
+        label = out.argmax(dim=1)
+        conf = F.softmax(out, dim=1).gather(1, label.unsqueeze(1))
+        host = torch.cat([out.float(), conf.float(), label.unsqueeze(1).float()], dim=1).cpu()
+        C = out.shape[1]
+        return host[:, :C], host[:, C + 1].long().tolist(), host[:, C].tolist()
+
+    def _view(self, toggles):
+        toggles = sorted(toggles)
+        return self._start.with_flips([self._t_view] * len(toggles), toggles, self_loops=True) if toggles else self._start
+
+    def _forward_view(self, T, partners, feats):
+        """The surrogate's row t through a view of the start adjacency (any surrogate, valued graphs)."""
+        self._t_view = T.t
+        x = self._x
+        if feats:
+            if self._x_trial is None:
+                self._x_trial = self._x.clone()
+            x = self._x_trial
+            row = T.x0.copy()
+            for f, delta in feats.items():
+                row[f] = T.x0[f] + delta
+            x[T.t] = torch.from_numpy(row).to(x.dtype).to(x.device)
+        with torch.no_grad():
+            out = self.surrogate(x, self._view(partners))[[T.t]]
+        if feats:
+            x[T.t] = self._x[T.t]
+        return self._read(out)
+
+    # -------------------------------------------------------------------------------------------- the loop
+    @staticmethod
+    def _better(strategy):
+        if strategy in ("under", "under_kl"):
+            return lambda new, best: new < best
+        if strategy == "over":
+            return lambda new, best: new > best
+        raise ValueError(f"Unknown strategy: {strategy}. Supported: 'under', 'over', 'under_kl'")
+
+    def _accept(self, T, d, logits, label, conf, step, verbose):
+        if d[0] == "edge":
+            T.toggles.symmetric_difference_update({d[2]})
+            T.flips.append(d[2])
+        else:
+            f, new = d[2], d[3]
+            T.x[f] = new
+            delta = float(new) - float(T.x0[f])
+            if delta == 0.0:
+                T.changed.pop(f, None)
+                T.feature_flips.pop(f, None)
+            else:
+                T.changed[f] = delta
+                T.feature_flips[f] = float(new)
+        T.best_conf = conf
+        T.attack_times += 1
+        T.trace.append(dict(action=("Add" if d[1] else "Remove") + (" edge" if d[0] == "edge" else " feature"),
+                            index=d[2], logits=logits.clone(), label=label, confidence=conf, step=step))
+        if verbose:
+            print(f"Step {step + 1}: {'Add' if d[1] else 'Remove'} {'edge' if d[0] == 'edge' else 'feature'} "
+                  f"({T.t}, {d[2]})")
+            print(f"New Confidence: {conf:.4f}")
+            print(f"Best Confidence: {T.best_conf:.4f}")
+
+    def _run(self, targets, n_perturbations, strategy, max_trials, verbose):
+        """The targets in lock step.  Fast path: one launch and one host read per step for all of them."""
+        better = self._better(strategy)
+        if self._local is not None:
+            _, labels, confs = self._launch([(T.t, [], None) for T in targets])
+        else:
+            labels, confs = [], []
+            for T in targets:
+                _, lab, cf = self._forward_view(T, [], None)
+                labels.append(lab[0])
+                confs.append(cf[0])
+        for T, lab, cf in zip(targets, labels, confs):
+            T.label, T.best_conf, T.conf0 = lab, cf, cf
+            T.evaluated = []                       # every evaluated trial: (step, draw, logits, label, confidence)
+            if verbose:
+                print("-" * 25, f"  {self._name} ATTACK BEGINS  ", "-" * 25)
+                print(f'Target Node: {T.t}')
+                print(f'Number of perturbations: {n_perturbations}')
+                print(f'Strategy: {strategy}')
+                print(f'Max trials per perturbation: {max_trials}')
+                print(f"Before Attack Label: {T.label}")
+                print(f"Before Attack Confidence: {T.best_conf:.4f}")
+                print("-" * 50)
+        for step in range(n_perturbations):
+            if self._local is not None:
+                drawn = [self._draw_step(T, max_trials) for T in targets]
+                specs, owner = [], []
+                for i, T in enumerate(targets):
+                    for k, d in enumerate(drawn[i][0]):
+                        if d is not None:
+                            specs.append((T.t,) + self._trial_spec(T, d))
+                            owner.append((i, k))
+                if specs:
+                    logits, labels, confs = self._launch(specs)
+                found = [False] * len(targets)
+                for row, (i, k) in enumerate(owner):
+                    if found[i]:
+                        continue
+                    T, d = targets[i], drawn[i][0][k]
+                    T.evaluated.append((step, d, logits[row], labels[row], confs[row]))
+                    if labels[row] == T.label and better(confs[row], T.best_conf):
+                        found[i] = True
+                        self._rewind(T, drawn[i][1], k)
+                        self._accept(T, d, logits[row], labels[row], confs[row], step, verbose)
+            else:
+                found = []
+                for T in targets:
+                    present = T.present()
+                    occupied = sorted(set(present) | {T.t})
+                    ok = False
+                    for _ in range(max_trials):
+                        d = self._draw(T, present, occupied)
+                        if d is None:
+                            continue
+                        logits, lab, cf = self._forward_view(T, *self._trial_spec(T, d))
+                        T.evaluated.append((step, d, logits[0], lab[0], cf[0]))
+                        if lab[0] == T.label and better(cf[0], T.best_conf):
+                            ok = True
+                            self._accept(T, d, logits[0], lab[0], cf[0], step, verbose)
+                            break
+                    found.append(ok)
+            if verbose:
+                for T, ok in zip(targets, found):
+                    if not ok:
+                        print(f"Step {step + 1}: No improvement found after {max_trials} trials")
+
+    def _result(self, T):
+        best = sorted(T.toggles)
+        r = dict(target=T.t, flips=T.flips, best_flips=best, feature_flips=dict(T.feature_flips), trace=T.trace,
+                 n_perturb=T.attack_times, best_conf=T.best_conf, original_label=T.label, original_conf=T.conf0,
+                 evaluated=T.evaluated,
+                 modified_op=self._start.with_flips([T.t] * len(best), best, self_loops=True))
+        if T.changed:
+            x = self._x_in.clone() if torch.is_tensor(self._x_in) else self._x.clone()
+            x[T.t] = torch.from_numpy(T.x).to(x.dtype).to(x.device)
+            r["modified_features"] = x
+        else:
+            r["modified_features"] = self._x_in
+        if self._dense is not None:
+            adj = self._dense.clone()
+            present = set(T.base_row)
+            for j in best:                          # calib_random.py:382-390: set to 1 or to 0, both entries
+                adj[T.t, j] = adj[j, T.t] = 0 if j in present else 1
+            r["modified_adj"] = adj
+        return r
+
+    def _publish(self, r, kwargs):
+        self.target_node = r["target"]
+        self.flips, self.best_flips, self.feature_flips = r["flips"], r["best_flips"], r["feature_flips"]
+        self.trace, self.evaluated = r["trace"], r["evaluated"]
+        self.modified_op, self.modified_features = r["modified_op"], r["modified_features"]
+        if "modified_adj" in r:
+            self.__dict__["modified_adj"] = r["modified_adj"]
+        kwargs.setdefault("n_perturb", []).append(r["n_perturb"])
+        kwargs.setdefault("best_conf", []).append(r["best_conf"])
+
+    def attack(self, ori_features, ori_adj, target_node, n_perturbations, strategy=None, max_trials=100, verbose=False,
+               **kwargs):
+        """``calib_random.py:46-203`` / ``calib_rnd.py:78-254``, drawing from the global ``random`` stream.  The lists
+        ``n_perturb`` / ``best_conf`` given as keywords are appended to."""
+        import random
+        strategy = self._default_strategy if strategy is None else strategy
+        self._better(strategy)
+        self._begin(ori_features, ori_adj)
+        T = self._new_target(target_node, random)
+        self._run([T], int(n_perturbations), strategy, int(max_trials), verbose)
+        r = self._result(T)
+        self._publish(r, kwargs)
+        if verbose:
+            print("-" * 50)
+            print(f"Attack completed with {r['n_perturb']} perturbations")
+            print(f"Final confidence: {r['best_conf']:.4f}")
+            print("-" * 50)
+
+    def attack_many(self, ori_features, ori_adj, targets, n_perturbations, strategy=None, max_trials=100, verbose=False,
+                    seed=None):
+        """``attack`` for several targets of one graph in lock step: one ``wg_trial_logits`` launch of
+        ``len(targets) * max_trials`` trials and one host read per step.  Each target draws from its own
+        ``random.Random``: ``seed`` is a list of one seed per target, an int that a ``random.Random`` turns into them,
+        or None for one draw of the global stream per target.  Returns one dict per target (``seed`` among its keys);
+        a target's result is that of ``attack`` alone after ``random.seed`` of its seed."""
+        import random
+        strategy = self._default_strategy if strategy is None else strategy
+        self._better(strategy)
+        targets = [int(t) for t in targets]
+        if seed is None:
+            seeds = [random.randrange(2 ** 63) for _ in targets]
+        elif isinstance(seed, (list, tuple)):
+            if len(seed) != len(targets):
+                raise ValueError("attack_many: one seed per target expected")
+            seeds = [int(s) for s in seed]
+        else:
+            src = random.Random(int(seed))
+            seeds = [src.randrange(2 ** 63) for _ in targets]
+        self._begin(ori_features, ori_adj)
+        states = [self._new_target(t, random.Random(s)) for t, s in zip(targets, seeds)]
+        if self._local is not None:
+            self._run(states, int(n_perturbations), strategy, int(max_trials), verbose)
+        else:
+            for T in states:
+                self._run([T], int(n_perturbations), strategy, int(max_trials), verbose)
+        results = []
+        for T, s in zip(states, seeds):
+            r = self._result(T)
+            r["seed"] = s
+            results.append(r)
+        return results
+
+
+class Calib_Random(_RandomAttack):
+    """``Calib_Random`` of the reference (``calib_attack/calib_random.py``) on the sparse path (DESIGN.md 4.3 "Random
+    trials"): the same constructor and ``attack``.  A step's ``max_trials`` trials are drawn ahead with the reference's
+    ``random`` calls in the reference's order, evaluated by one ``wg_trial_logits`` launch, the first accepted one is
+    taken and the random state is put back to where the reference would have stopped drawing.  ``ori_adj``: a dense
+    tensor, a ``RowNormalizedAdjacency`` or a ``FlippedAdjacency``.
+
+    Fast path: a bare ``SparseCompatibleGCN``, an unfused ``WATS`` over one (structure trials only) or a calibrator of
+    ``scaling.py``, on a unit graph with ``Hd, C <= 256``.  Everything else, and ``local_eval=False``, evaluates trial
+    by trial through ``with_flips`` views; on a valued graph a removal there is the view's ``1 - 2 a`` toggle, which
+    is the reference's "set to 0" only for entries equal to 1.  Results: ``flips`` / ``best_flips`` (partners, ``t``
+    itself for its self loop), ``feature_flips`` (``{f: value}``), ``trace`` (per accepted step), ``evaluated`` (every
+    evaluated trial), ``modified_op``, ``modified_features``, ``modified_adj`` (dense input only)."""
+
+    _default_strategy = "under"
+    _name = "CALIB_RANDOM"
+
+
+class Calib_RND(_RandomAttack):
+    """``Calib_RND`` of the reference (``calib_attack/calib_rnd.py``): the same trials as ``Calib_Random`` (its
+    ``random.choice`` of an array takes the draw ``random.randint`` takes there), ``under_kl`` by default, scipy /
+    numpy inputs accepted, ``modified_adj`` as a scipy CSR when the input was scipy, numpy or a dense tensor.
+    Not kept: ``check_adj``'s dense test.  ``random_node_injection`` is not built: it changes ``n``."""
+
+    _default_strategy = "under_kl"
+    _name = "CALIB_RND"
+
+    def _operator(self, ori_adj):
+        import numpy as np
+        import scipy.sparse as sp
+        self._scipy_out = True
+        if sp.issparse(ori_adj):
+            M = sp.csr_matrix(ori_adj, dtype=np.float32)
+            M.sum_duplicates()
+            M.eliminate_zeros()
+            M.sort_indices()
+            unit = bool((M.data == 1).all())
+            op = RowNormalizedAdjacency(M.shape[0], torch.from_numpy(M.indptr.astype(np.int64)).to(self.device),
+                                        torch.from_numpy(M.indices.astype(np.int32)).to(self.device),
+                                        None if unit else torch.from_numpy(M.data).to(self.device), device=self.device)
+            return op, None
+        if isinstance(ori_adj, np.ndarray):
+            ori_adj = torch.from_numpy(np.asarray(ori_adj, np.float32))
+        if isinstance(ori_adj, RowNormalizedAdjacency):
+            self._scipy_out = False
+        return super()._operator(ori_adj)
+
+    def _features(self, ori_features):
+        import numpy as np
+        import scipy.sparse as sp
+        if sp.issparse(ori_features):
+            return torch.from_numpy(np.asarray(ori_features.todense(), np.float32))
+        if isinstance(ori_features, np.ndarray):
+            return torch.from_numpy(np.asarray(ori_features, np.float32))
+        return ori_features
+
+    def _result(self, T):
+        import scipy.sparse as sp
+        r = super()._result(T)
+        if self._scipy_out:
+            indptr, indices, values = r["modified_op"].csr()
+            r["modified_adj"] = sp.csr_matrix((values.cpu().numpy(), indices.cpu().numpy(), indptr.cpu().numpy()),
+                                              shape=(self._n, self._n))
+        return r
+
+    def random_node_injection(self, *args, **kwargs):
+        raise NotImplementedError("Calib_RND.random_node_injection adds nodes: it changes n, which neither the "
+                                  "with_flips views nor wg_trial_logits model (DESIGN.md 8, \"Not built\")")

@@ -60,15 +60,16 @@ def _upload(device, arrays: dict) -> dict:
     return {k: dev[offs[k]:offs[k] + t.numel() * t.element_size()].view(t.dtype) for k, t in arrays.items()}
 
 
-def _pairs(n: int, rows, cols):
-    """The pairs of one flip call as host int64 tensors, validated as ``toggle_edges`` validates them."""
+def _pairs(n: int, rows, cols, self_loops: bool = False):
+    """The pairs of one flip call as host int64 tensors, validated as ``toggle_edges`` validates them
+    (``self_loops``: a pair ``r == c`` is taken and flips the one diagonal entry)."""
     r = torch.as_tensor(rows).detach().cpu().to(torch.int64).reshape(-1)
     c = torch.as_tensor(cols).detach().cpu().to(torch.int64).reshape(-1)
     if r.shape != c.shape:
         raise ValueError("rows and cols must have the same length")
     if r.numel() and (int(torch.minimum(r.min(), c.min())) < 0 or int(torch.maximum(r.max(), c.max())) >= n):
         raise ValueError(f"pair outside [0, {n})")
-    if bool((r == c).any()):
+    if not self_loops and bool((r == c).any()):
         raise ValueError("with_flips: r == c (the attack never flips a self loop, calib_fga.py:897)")
     unordered = torch.minimum(r, c) * n + torch.maximum(r, c)
     if torch.unique(unordered).numel() != unordered.numel():
@@ -174,11 +175,13 @@ class FlippedAdjacency(RowNormalizedAdjacency):
     # ------------------------------------------------------------------ construction
     @classmethod
     def compose(cls, base: RowNormalizedAdjacency, prev: "FlippedAdjacency | None", rows, cols,
-                symmetric: bool = True) -> "FlippedAdjacency":
-        """``prev`` (a view of ``base``, or None for ``base`` itself) after one more flip call."""
+                symmetric: bool = True, self_loops: bool = False) -> "FlippedAdjacency":
+        """``prev`` (a view of ``base``, or None for ``base`` itself) after one more flip call.  ``self_loops``
+        admits pairs ``r == c`` (the random attacks remove a target's self loop, ``calib_random.py:386-390``): the
+        two positions of such a pair are one, flipped once."""
         device = require_gpu(base.device)
         n = base.n
-        r, c = _pairs(n, rows, cols)
+        r, c = _pairs(n, rows, cols, self_loops)
         k_rc, k_cr = r * n + c, c * n + r
         old_keys = prev._keys if prev is not None else torch.empty(0, dtype=torch.int64)
         keys = torch.unique(torch.cat([old_keys, k_rc, k_cr] if symmetric else [old_keys, k_rc]))  # ascending
@@ -218,9 +221,9 @@ class FlippedAdjacency(RowNormalizedAdjacency):
         return cls(base, keys[keep], a_old[keep].contiguous(), a_new[keep].contiguous(), base_pos[keep].contiguous(),
                    row_sum[seg_of][keep].contiguous())
 
-    def with_flips(self, rows, cols, symmetric: bool = True) -> "FlippedAdjacency":
+    def with_flips(self, rows, cols, symmetric: bool = True, self_loops: bool = False) -> "FlippedAdjacency":
         """This view after one more flip call (``calib_fga.py:901-904``), on the same parent."""
-        return FlippedAdjacency.compose(self.base, self, rows, cols, symmetric)
+        return FlippedAdjacency.compose(self.base, self, rows, cols, symmetric, self_loops)
 
     def flipped(self, rows, cols, symmetric: bool = True) -> RowNormalizedAdjacency:
         return self.with_flips(rows, cols, symmetric).materialize()

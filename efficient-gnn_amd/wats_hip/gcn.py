@@ -234,13 +234,14 @@ class RowNormalizedAdjacency:
         indptr, indices, values = toggle_edges(self.n, self.indptr, self.indices, self.values, rows, cols, symmetric)
         return RowNormalizedAdjacency(self.n, indptr, indices, values, reorder=self.reorder, device=self.device)
 
-    def with_flips(self, rows, cols, symmetric: bool = True):
+    def with_flips(self, rows, cols, symmetric: bool = True, self_loops: bool = False):
         """The same flip as a view (``wats_hip.flips.FlippedAdjacency``): this operator's handles plus an
         overlay of the flipped positions, for a candidate that is propagated once or twice
-        (``calib_fga.py:901-913``).  ``view.materialize()`` builds the real operator."""
+        (``calib_fga.py:901-913``).  ``view.materialize()`` builds the real operator.  ``self_loops=True``
+        admits pairs ``r == c``, refused otherwise."""
         require_gpu(getattr(self, "device", None))
         from .flips import FlippedAdjacency
-        return FlippedAdjacency.compose(self, None, rows, cols, symmetric)
+        return FlippedAdjacency.compose(self, None, rows, cols, symmetric, self_loops)
 
     def dense_row(self, t: int) -> torch.Tensor:
         """Row ``t`` of ``adj`` as a dense float32 vector of length n."""

@@ -920,6 +920,31 @@ int wg_edge_pair_inv_distance(int64_t nnz, const int32_t* rows, const int32_t* c
  * aligned.  1 <= Hd, C <= 256, B >= 1; n or nnz above int32:
  * WG_ERR_UNSUPPORTED.  An empty S_b gives the base model's row t.
  * Asynchronous, no allocation, capturable.
+ *
+ * wg_trial_logits: the logits of B trials of the random attacks in one launch
+ * (calib_attack/calib_random.py:127-186, calib_rnd.py:169-236: every trial is a
+ * full forward there).  The same kernel and the same sums as wg_target_logits,
+ * with three things per trial b:
+ *   trial_t[b] (int32)  its own target t; trials of one launch may name
+ *                       different targets, and duplicates are allowed
+ *   S_b                 as above, but j == t is allowed and toggles the single
+ *                       diagonal entry (t, t) (the reference lists t among the
+ *                       connected nodes of a row with a self loop): N'(t) =
+ *                       N(t) delta S_b, N'(j) = N(j) delta {t} for j != t in S_b
+ *   F_b = feat_ids[feat_ptr[b] .. feat_ptr[b + 1]) (int32, ascending, no
+ *         duplicates, inside [0, nfeat)) with feat_delta (float32, one per id):
+ *         deltas of the target's own feature row.  In float64
+ *           dz_b[h] = sum_{f in F_b ascending} (double)feat_delta * (double)W1[h, f]
+ *         with W1 (Hd, nfeat), and y1_j = (1 / deg'_j) (sum_{k in N'(j)} z_k + dz_b)
+ *         for every j in N'(t) whose row N'(j) holds t (the self loop j == t
+ *         included; asked of the row itself, no symmetry is assumed), that is
+ *         z_t + dz_b wherever row t of z is gathered.
+ * feat_ptr == NULL: no feature trial in the launch; W1, feat_ids, feat_delta
+ * and nfeat are then not read.  With every trial_t[b] equal, no t in any S_b
+ * and no features, out has wg_target_logits' bits.  trial_t, the ids of S_b
+ * and F_b are checked on the device in the bounds-checked variant only; every
+ * other argument before any device call (1 <= Hd, C <= 256, B >= 1, nfeat >= 1
+ * with features).  Asynchronous, no allocation, capturable.
  * ---------------------------------------------------------------------- */
 int wg_flip_select_workspace(int64_t* bytes);
 int wg_flip_select(int64_t n, int64_t t, const float* grad_loss, const float* grad_pmax,
@@ -932,6 +957,12 @@ int wg_target_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_
                      int64_t Hd, const float* z, const float* b1, const float* W2, const float* b2,
                      int64_t C, int64_t t, int64_t B, const int32_t* cand_ptr,
                      const int32_t* cand_ids, float* out, void* stream);
+int wg_trial_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
+                    int64_t Hd, const float* z, const float* b1, const float* W2, const float* b2,
+                    int64_t C, int64_t B, const int32_t* trial_t, const int32_t* cand_ptr,
+                    const int32_t* cand_ids, int64_t nfeat, const float* W1,
+                    const int32_t* feat_ptr, const int32_t* feat_ids, const float* feat_delta,
+                    float* out, void* stream);
 
 /* ----------------------------------------------------------------------
  * The integrated-gradient scores of calib_attack/calib_iga.py on the sparse
