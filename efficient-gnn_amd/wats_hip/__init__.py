@@ -26,7 +26,8 @@ GETSCalibrator / GCNExpert / gated_sym_norm_head / calibrate_with_gets (the mixt
 last propagation of every expert, the top-k gated mixture, softplus and log_softmax as one HIP pass that reads only
 the selected slices, no (N, E, C) tensor of aggregated outputs), Calib_FGA / flip_select / target_logits (the
 reference's calibration attack as a drop-in class on the sparse path: the flip selection in one HIP pass and the
-candidate's logits from the 2-hop ball of the target), Calib_IGA / iga_path_logits / iga_scores (the reference's
+candidate's logits from the 2-hop ball of the target; Calib_FGA.attack_many / fga_scores run many targets in lock
+step with the gradient's row and column in closed form, one HIP pass over z and h for all of them), Calib_IGA / iga_path_logits / iga_scores (the reference's
 integrated-gradients attack: its path integrals in closed form, all targets scored in one HIP pass over z and h),
 Calib_Random / Calib_RND / trial_logits (the reference's random baseline attacks: a step's trials drawn ahead from
 the reference's own random stream and evaluated by one HIP launch, several targets in lock step),
@@ -67,6 +68,8 @@ from .attack import (  # noqa: F401
     Calib_IGA,
     Calib_Random,
     Calib_RND,
+    fga_scores,
+    fga_scores_workspace,
     flip_select,
     iga_path_logits,
     iga_scores,

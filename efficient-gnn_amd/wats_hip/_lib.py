@@ -97,6 +97,10 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp, c_vp]),
     "wg_trial_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
                                        c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wg_fga_scores_workspace": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_fga_scores": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
+                                     c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp]),
     "wg_iga_max_topk": (ctypes.c_int, []),
     "wg_iga_path_logits": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_i64, c_i64, c_vp, c_i32, c_vp,
                                                                                         c_vp, c_vp]),

@@ -25,6 +25,10 @@ confidence, ascending), ``modified_op`` (that adjacency as a view: ``.materializ
 ``modified_adj`` (a dense tensor when ``ori_adj`` was dense; otherwise ``AttributeError``), ``trace`` (one dict per
 evaluated candidate: partner, logits row, label, confidence).
 
+``Calib_FGA.attack_many`` runs one of the four methods for many targets of one graph in lock step (DESIGN.md 4.3
+"Batched attack step"): the gradient's row and column in closed form by :func:`fga_scores` (``wg_fga_scores``,
+``csrc/fga.hip``), the children by ``wg_trial_logits``, no whole-graph pass in the loop.
+
 Further down: ``Calib_IGA`` (``calib_attack/calib_iga.py``) and the random baselines ``Calib_Random`` / ``Calib_RND``
 (``calib_attack/calib_random.py``, ``calib_rnd.py``; DESIGN.md 4.3 "Random trials") with ``trial_logits``
 (``wg_trial_logits``: all trials of a step in one launch).
@@ -164,6 +168,173 @@ def target_logits(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.
                                            ptr(cand_ids) if cand_ids.numel() else None, ptr(out),
                                            stream_handle(device)), "target_logits")
     return out
+
+
+def fga_scores_workspace(n: int, Hd: int, B: int, G: int, local_cap: int, device) -> torch.Tensor:
+    """The buffer of ``wg_fga_scores``: the coefficients, the local lists (``local_cap`` entries: at least the sum over
+    the targets of ``|N(t)| + |S_b|``) and the partial top-k lists."""
+    nbytes = ctypes.c_int64(0)
+    check(_lib.load().wg_fga_scores_workspace(n, Hd, B, G, local_cap, ctypes.byref(nbytes)), "fga_scores_workspace")
+    return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+
+
+def _pack_toggles(n, targets, toggles, device):
+    """(targets, tog_ptr, tog_ids) int32 on the device (one copy) from host lists, checked"""
+    ptrs, ids = [0], []
+    for t, S in zip(targets, toggles):
+        S = [int(j) for j in S]
+        if not 0 <= int(t) < n:
+            raise ValueError(f"target {t} outside [0, {n})")
+        if any(b <= a for a, b in zip(S, S[1:])) or any(j == int(t) or not 0 <= j < n for j in S):
+            raise ValueError("a target's toggled partners must be ascending, distinct, inside [0, n) and not the target")
+        ids += S
+        ptrs.append(len(ids))
+    from .flips import _upload
+    d = _upload(device, dict(t=torch.tensor([int(t) for t in targets], dtype=torch.int32),
+                             ptr=torch.tensor(ptrs, dtype=torch.int32), ids=torch.tensor(ids, dtype=torch.int32)))
+    return d["t"], d["ptr"], d["ids"]
+
+
+def fga_scores(n: int, indptr: torch.Tensor, indices: torch.Tensor, z: torch.Tensor, h: torch.Tensor, b1: torch.Tensor,
+               W2: torch.Tensor, targets, toggles, g_logits: torch.Tensor, rerank: torch.Tensor | None = None,
+               p_top2: torch.Tensor | None = None, topk: int = 1, n_workgroups: int = 0, return_grads: bool = False,
+               return_scores: bool = False, workspace: torch.Tensor | None = None, local_cap: int | None = None):
+    """``wg_fga_scores``: ``(best_ids int32 (B, topk), best_scores float32 (B, topk))`` and, on request, the gradients
+    ``(B, G, 2 n)`` in the target probe's layout and the score matrix ``(B, n)`` (``calib_fga.py:864-898`` for every
+    target in one pass over ``z`` and ``h``).  ``targets`` / ``toggles``: host lists (a target and its ascending
+    toggled partners), or int32 device tensors ``targets`` and ``toggles = (tog_ptr, tog_ids)`` that the caller
+    checked.  ``g_logits (B, G, C)``: d L / d out_t of the loss and, with ``G == 3``, of ``p_max`` and ``p_smax``;
+    ``rerank`` int32 ``[B]`` and ``p_top2 (B, 2)`` go with ``G == 3``.  ``local_cap``: see ``fga_scores_workspace``
+    (computed with one host read when not given)."""
+    device = require_gpu(z.device if z.is_cuda else None)
+    if isinstance(toggles, tuple):
+        tog_ptr, tog_ids = toggles
+    else:
+        targets, tog_ptr, tog_ids = _pack_toggles(n, targets, toggles, device)
+    B, Hd, C = int(targets.numel()), int(z.shape[1]), int(W2.shape[0])
+    if g_logits.dim() != 3 or g_logits.shape[0] != B or g_logits.shape[2] != C or int(tog_ptr.numel()) != B + 1:
+        raise ValueError("fga_scores: g_logits (B, G, C) and tog_ptr [B + 1] of the same targets expected")
+    G = int(g_logits.shape[1])
+    if z.shape[0] != n or h.shape != z.shape or W2.shape[1] != Hd or b1.numel() != Hd:
+        raise ValueError("fga_scores: z, h (n, Hd), b1 [Hd], W2 (C, Hd) expected")
+    if rerank is not None and (G != 3 or p_top2 is None or tuple(p_top2.shape) != (B, 2) or rerank.numel() != B):
+        raise ValueError("fga_scores: rerank [B] needs G == 3 and p_top2 (B, 2)")
+    if local_cap is None:
+        tl = targets.long()
+        local_cap = int((indptr[tl + 1] - indptr[tl]).sum()) + int(tog_ids.numel())
+    best_ids = torch.empty((B, topk), dtype=torch.int32, device=device)
+    best_scores = torch.empty((B, topk), dtype=torch.float32, device=device)
+    grads = torch.empty((B, G, 2 * n), dtype=torch.float32, device=device) if return_grads else None
+    scores = torch.empty((B, n), dtype=torch.float32, device=device) if return_scores else None
+    if workspace is None:
+        workspace = fga_scores_workspace(n, Hd, B, G, local_cap, device)
+    nnz = int(indices.numel())
+    with torch.cuda.device(device):
+        check(_lib.load().wg_fga_scores(n, nnz, ptr(indptr), ptr(indices) if nnz else None, Hd, ptr(z), ptr(h), ptr(b1),
+                                        ptr(W2), C, B, ptr(targets), ptr(tog_ptr),
+                                        ptr(tog_ids) if tog_ids.numel() else None, G, ptr(g_logits), ptr(rerank),
+                                        ptr(p_top2), topk, n_workgroups, local_cap, ptr(workspace), ptr(grads),
+                                        ptr(scores), ptr(best_ids), ptr(best_scores), stream_handle(device)),
+              "fga_scores")
+    out = (best_ids, best_scores)
+    if return_grads:
+        out += (grads,)
+    if return_scores:
+        out += (scores,)
+    return out
+
+
+def _loss_rows(out, kinds, labels, res_gt=None):
+    """The criteria of ``Calib_FGA`` applied to each row of ``out (B, C)`` on its own (a batch of one: the mean of one
+    value), as a vector ``[B]``: ``kinds[b]`` is ``over`` / ``under`` (the two objectives), ``kl`` (``kl_divergence_
+    with_uniform``), ``target`` (``kl_divergence_target`` with ``labels[b]`` as the target label and ``res_gt[b]``) or
+    ``restore`` (``-nll_loss``).  A row's gradient does not depend on which rows share the call."""
+    loss = out.new_zeros(out.shape[0])
+    n_classes = out.shape[1]
+    for kind in sorted(set(kinds)):
+        # each criterion on its own rows only: a row never meets the log of another kind's underflowed probability
+        where = [b for b, k in enumerate(kinds) if k == kind]
+        idx = torch.tensor(where, device=out.device)
+        o, lab = out[idx], labels[idx]
+        rows = torch.arange(len(where), device=out.device)
+        if kind == "restore":
+            value = o[rows, lab]
+        else:
+            probs = F.softmax(o, dim=1)
+            own = probs[rows, lab]
+            if kind == "over":
+                value = -(1 - own)
+            elif kind == "under":
+                keep = torch.ones_like(probs)
+                keep[rows, lab] = 0
+                others, _ = torch.max(probs * keep, dim=1)
+                value = -(own - others)
+            else:
+                dist = torch.full_like(probs, 1.0 / n_classes)
+                if kind == "target":
+                    predicted = torch.argmax(probs, dim=1)
+                    for i, b in enumerate(where):
+                        tl, pred, gt = int(lab[i]), int(predicted[i]), int(res_gt[b])
+                        dist[i] = 0.0
+                        if pred == tl:
+                            if gt == tl:
+                                dist[i] = 1.0 / n_classes
+                            else:
+                                dist[i, tl] = 1.0
+                        elif gt != tl:
+                            dist[i] = 1.0 / (n_classes - 1)
+                            dist[i, tl] = 0.0
+                        else:
+                            dist[i, tl] = 0.5
+                            dist[i, pred] = 0.5
+                value = -F.kl_div(probs.log(), dist, reduction='none').sum(dim=1)
+        loss = loss.index_put((idx,), value)
+    return loss
+
+
+def _row_gradients(raw, head, kinds, labels, rerank, res_gt=None):
+    """``g_logits (B, G, C)`` = d / d raw of each row's loss and, where any row reranks (``G == 3``), of its ``p_max``
+    and ``p_smax`` (``calib_fga.py:877-890`` on the ``(B, C)`` block of base logits ``raw`` under the calibrator's
+    row map ``head``), and ``p_top2 (B, 2)``."""
+    leaf = raw.detach().clone().requires_grad_(True)
+    out = head(leaf)
+    loss = _loss_rows(out, kinds, labels, res_gt).sum()
+    need = any(rerank)
+    gs = [torch.autograd.grad(loss, leaf, retain_graph=need, allow_unused=True)[0]]
+    top2 = None
+    if need:
+        top2 = torch.topk(F.softmax(out, dim=1), 2, dim=1)[0]
+        gs.append(torch.autograd.grad(top2[:, 0].sum(), leaf, retain_graph=True)[0])
+        gs.append(torch.autograd.grad(top2[:, 1].sum(), leaf)[0])
+        top2 = top2.detach().contiguous()
+    gs = [torch.zeros_like(leaf) if g is None else g for g in gs]
+    return torch.stack(gs, dim=1).contiguous(), top2
+
+
+class _ManyResult(dict):
+    """One target's result of ``attack_many``; ``modified_op`` is made when it is first read with ``r["modified_op"]``
+    or ``r.get("modified_op")`` (a ``with_flips`` view).  ``keys()``, ``items()`` and ``dict(r)`` hold it only after
+    that first read."""
+
+    def __init__(self, start, **fields):
+        super().__init__(**fields)
+        self._start = start
+
+    def __missing__(self, key):
+        if key != "modified_op":
+            raise KeyError(key)
+        best = self["best_flips"]
+        self[key] = self._start.with_flips([self["target"]] * len(best), best)
+        return self[key]
+
+    def __contains__(self, key):
+        return key == "modified_op" or super().__contains__(key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
+METHODS = ("attack", "rerank_attack", "rerank_hybridloss_attack", "flip_beam_hybridloss_attack")
 
 
 # ------------------------------------------------------------------------------------------------ the attack
@@ -580,6 +751,230 @@ class Calib_FGA(torch.nn.Module):
             raise ValueError("Final label does not match original label!")
         self._log_attack_summary(display_strategy, target_node, attack_times, n_perturbations, original_label_item,
                                  final_label, initial_confidence, final_confidence)
+
+    # -------------------------------------------------------------------------------------------- many targets
+    def attack_many(self, ori_features, ori_adj, targets, n_perturbations, strategy, *,
+                    method="flip_beam_hybridloss_attack", res_gt=None, target_label=0, beam_width=3, verbose=False,
+                    **kwargs):
+        """One of the four methods for several targets of one graph, every target starting from ``ori_adj`` (the
+        reference's per-node loop, ``exp/ablation/ugca_full_multi_dataset.py:372-411``).  The targets run in lock step,
+        each its own copy of the single-target state machine; a step is one ``wg_trial_logits`` launch for the
+        children, autograd on the ``(B, C)`` block of logits and one ``wg_fga_scores`` call: no whole-graph pass.
+        Returns one dict per target, in target order: ``target``, ``flips``, ``best_flips``, ``n_perturb``,
+        ``best_conf``, ``original_label``, ``final_label``, ``final_confidence``, ``trace`` and ``modified_op`` (made
+        when first read by key or ``get``; iterating the dict shows it only after that).  Where ``wg_target_logits``
+        does not apply (``_local_model``) the single-target method is called per target and the same dicts are
+        returned."""
+        if method not in METHODS:
+            raise ValueError(f"Unknown method: {method}")
+        if method != "attack" and strategy != 'under':
+            raise ValueError(f"{method} only supports 'under' strategy, got '{strategy}'")
+        if method == "attack" and strategy not in ('over', 'under', 'under_kl', 'target', 'max'):
+            raise ValueError(f"Unknown strategy: {strategy}")
+        if res_gt is None:
+            raise ValueError("res_gt must be provided for Calib_FGA attacks")
+        targets = [int(t) for t in targets]
+        if not targets:
+            return []
+        start_time = time.time()
+        self._begin(ori_features, ori_adj, targets[0])
+        for t in targets:
+            if not 0 <= t < self._n:
+                raise ValueError(f"target {t} outside [0, {self._n})")
+        if self._local is None or (method == "attack" and strategy == 'max'):
+            results = self._many_by_loop(ori_features, ori_adj, targets, n_perturbations, strategy, method, res_gt,
+                                         target_label, beam_width, verbose)
+        else:
+            results = self._many_local(targets, int(n_perturbations), strategy, method, res_gt, target_label,
+                                       int(beam_width))
+        elapsed = time.time() - start_time
+        for r in results:
+            kwargs.get("n_perturb", []).append(r["n_perturb"])
+            kwargs.get("best_conf", []).append(r["best_conf"])
+            if method == "flip_beam_hybridloss_attack":
+                kwargs.get("runtime", []).append(elapsed / len(results))
+            if verbose:
+                self._log_attack_summary(strategy, r["target"], r["n_perturb"], n_perturbations, r["original_label"],
+                                         r["final_label"], r["original_confidence"], r["final_confidence"])
+        if method == "flip_beam_hybridloss_attack":
+            for r in results:
+                if r["final_label"] != r["original_label"]:
+                    raise ValueError("Final label does not match original label!")
+        return results
+
+    def _many_by_loop(self, ori_features, ori_adj, targets, n_perturbations, strategy, method, res_gt, target_label,
+                      beam_width, verbose):
+        """The single-target method per target (any surrogate, valued graphs, ``local_eval=False``)."""
+        import contextlib
+        import io
+        results = []
+        for t in targets:
+            kw = dict(n_perturb=[], best_conf=[])
+            if method == "flip_beam_hybridloss_attack":
+                kw["beam_width"] = beam_width
+            with contextlib.nullcontext() if verbose else contextlib.redirect_stdout(io.StringIO()):
+                try:
+                    getattr(self, method)(ori_features, ori_adj, t, n_perturbations, strategy,
+                                          target_label=target_label, res_gt=res_gt, verbose=verbose, **kw)
+                except ValueError as e:                # raised by attack_many after every target has run
+                    if "Final label" not in str(e):
+                        raise
+                with torch.no_grad():
+                    first = self._evaluate_start()
+                    last = self.surrogate(self._x, self._view(self.best_flips))[[t]]
+            label0, label1 = int(first.argmax(dim=1)), int(last.argmax(dim=1))
+            results.append(_ManyResult(
+                self._start, target=t, flips=list(self.flips), best_flips=list(self.best_flips),
+                n_perturb=kw["n_perturb"][0], best_conf=kw["best_conf"][0], original_label=label0,
+                original_confidence=float(F.softmax(first, dim=1)[0, label0]), final_label=label1,
+                final_confidence=float(F.softmax(last, dim=1)[0, label1]),
+                trace=[{k: s[k] for k in ("partner", "logits", "label", "confidence")} for s in self.trace]))
+        return results
+
+    def _many_local(self, targets, budget, strategy, method, res_gt, target_label, beam_width):
+        model, wats = self._local
+        device, n = self.device, self._n
+        indptr, indices, _ = self._csr
+        w1 = model.gc1.weight
+        key = (self._x.data_ptr(), self._x._version, tuple(self._x.shape), w1.data_ptr(), w1._version)
+        with torch.no_grad():
+            if self._z_key != key:
+                self._z, self._z_key = (self._x.to(torch.float32) @ w1.t()).contiguous(), key
+            z = self._z
+            b1, W2, b2 = model.gc1.bias.detach(), model.gc2.weight.detach().contiguous(), model.gc2.bias.detach()
+            h = F.relu(self._start @ z + b1).contiguous()           # the base graph's hidden rows, once per call
+            node = torch.tensor(targets, dtype=torch.int64, device=device)
+            temps = None
+            if wats is not None and not hasattr(wats, "row_map"):
+                temps = wats.temperatures()
+            start_out = self.surrogate(self._x, self._start).detach()[node]
+        row_len = (indptr[node + 1] - indptr[node]).cpu().tolist()
+        gt = res_gt.to(device)[node]
+
+        def head_of(rows):
+            """the calibrator's row map of a (len(rows), C) block of base logits; rows: positions in `targets`"""
+            if wats is None:
+                return lambda raw: raw
+            if temps is None:
+                return wats.row_map
+            tr = temps[node[rows]].unsqueeze(1)
+            return lambda raw: F.log_softmax(raw / tr, dim=1)
+
+        def evaluate(rows, sets):
+            """one launch: (raw logits on the device, head outputs, labels and confidences on the host)"""
+            with torch.no_grad():
+                raw = trial_logits(n, indptr, indices, z, b1, W2, b2, [(targets[r], sorted(S), None)
+                                                                      for r, S in zip(rows, sets)])
+                out = head_of(rows)(raw)
+                host, labels, confs = _RandomAttack._read(out)
+            return raw, host, labels, confs
+
+        def scored_step(rows, sets, raws, kinds, labels, rerank):
+            """the partner every member flips next (one wg_fga_scores call)"""
+            g, top2 = _row_gradients(raws, head_of(rows), kinds, labels, rerank,
+                                     gt[rows] if "target" in kinds else None)
+            tg, tog_ptr, tog_ids = _pack_toggles(n, [targets[r] for r in rows], [sorted(S) for S in sets], device)
+            rr = torch.tensor([int(v) for v in rerank], dtype=torch.int32).to(device) if top2 is not None else None
+            cap = sum(row_len[r] + len(S) for r, S in zip(rows, sets))
+            best_ids, _ = fga_scores(n, indptr, indices, z, h, b1, W2, tg, (tog_ptr, tog_ids), g, rr, top2, topk=1,
+                                     local_cap=cap)
+            return best_ids[:, 0].cpu().tolist()
+
+        B = len(targets)
+        label0 = start_out.argmax(dim=1).cpu().tolist()
+        conf0 = F.softmax(start_out, dim=1).gather(1, start_out.argmax(dim=1, keepdim=True))[:, 0].cpu().tolist()
+        flips, trace = [[] for _ in targets], [[] for _ in targets]
+        best, best_conf, used = [frozenset()] * B, list(conf0), [0] * B
+        every = list(range(B))
+        raw0 = evaluate(every, [()] * B)[0] if budget > 0 else None
+
+        def record(r, j, host_row, label, conf):
+            flips[r].append(j)
+            trace[r].append(dict(partner=j, logits=host_row.clone(), label=label, confidence=conf))
+
+        if method == "flip_beam_hybridloss_attack":
+            seq = [0] * B
+            beams = [[(conf0[r], 0, 0, frozenset(), raw0[r])] for r in every] if budget > 0 else [[] for _ in every]
+            for _ in range(budget):
+                nexts = [[] for _ in every]
+                for _ in range(beam_width):
+                    rows, members = [], []
+                    for r in every:
+                        if not beams[r]:
+                            continue
+                        m = heapq.heappop(beams[r])
+                        if m[1] >= budget:
+                            continue
+                        rows.append(r)
+                        members.append(m)
+                    if not rows:
+                        break
+                    raws = torch.stack([m[4] for m in members])
+                    cur = head_of(rows)(raws).argmax(dim=1)
+                    same = (cur.cpu() == torch.tensor([label0[r] for r in rows])).tolist()
+                    kinds = ["kl" if s else "restore" for s in same]
+                    labels = torch.where(torch.tensor(same, device=device), cur,
+                                         torch.tensor([label0[r] for r in rows], device=device))
+                    js = scored_step(rows, [m[3] for m in members], raws, kinds, labels, same)
+                    children = [frozenset(self._toggle(m[3], j)) for m, j in zip(members, js)]
+                    raw, host, labs, confs = evaluate(rows, children)
+                    for i, r in enumerate(rows):
+                        record(r, js[i], host[i], labs[i], confs[i])
+                        seq[r] += 1
+                        count = members[i][1] + 1
+                        heapq.heappush(nexts[r], (confs[i], count, seq[r], children[i], raw[i]))
+                        if labs[i] == label0[r] and confs[i] < best_conf[r]:
+                            best_conf[r], best[r], used[r] = confs[i], children[i], count
+                beams = nexts
+        else:
+            active = list(every) if budget > 0 else []
+            sets = {r: frozenset() for r in active}
+            raws = {r: raw0[r] for r in active}
+            hybrid = method == "rerank_hybridloss_attack"
+            for _ in range(budget):
+                if not active:
+                    break
+                rows = active
+                block = torch.stack([raws[r] for r in rows])
+                cur = head_of(rows)(block).argmax(dim=1)
+                if method == "attack":
+                    kind = {"over": "over", "under": "under", "under_kl": "kl", "target": "target"}[strategy]
+                    kinds, rerank = [kind] * len(rows), [False] * len(rows)
+                    labels = torch.full_like(cur, int(target_label)) if kind == "target" else cur
+                else:
+                    same = (cur.cpu() == torch.tensor([label0[r] for r in rows])).tolist()
+                    calib = [s or not hybrid for s in same]
+                    kinds, rerank = ["kl" if c else "restore" for c in calib], calib
+                    labels = torch.where(torch.tensor(calib, device=device), cur,
+                                         torch.tensor([label0[r] for r in rows], device=device))
+                js = scored_step(rows, [sets[r] for r in rows], block, kinds, labels, rerank)
+                children = [frozenset(self._toggle(sets[r], j)) for r, j in zip(rows, js)]
+                raw, host, labs, confs = evaluate(rows, children)
+                still = []
+                for i, r in enumerate(rows):
+                    if labs[i] != label0[r]:                     # the label moved: this target stops here
+                        record(r, js[i], host[i], labs[i], float("nan"))
+                        continue
+                    record(r, js[i], host[i], labs[i], confs[i])
+                    used[r] += 1
+                    sets[r], raws[r] = children[i], raw[i]
+                    still.append(r)
+                    if method != "attack" or strategy in ('under', 'under_kl'):
+                        better = confs[i] <= best_conf[r]
+                    elif strategy == 'over':
+                        better = confs[i] >= best_conf[r]
+                    else:
+                        tl, g_t = int(target_label), int(gt[r])
+                        under = (tl == label0[r] and tl == g_t) or (tl != label0[r] and tl == g_t)
+                        better = confs[i] <= best_conf[r] if under else confs[i] >= best_conf[r]
+                    if better:
+                        best_conf[r], best[r] = confs[i], children[i]
+                active = still
+        _, _, final_labels, final_confs = evaluate(every, best)
+        return [_ManyResult(self._start, target=targets[r], flips=flips[r], best_flips=sorted(best[r]),
+                            n_perturb=used[r], best_conf=best_conf[r], original_label=label0[r],
+                            original_confidence=conf0[r], final_label=final_labels[r],
+                            final_confidence=final_confs[r], trace=trace[r]) for r in every]
 
 
 # ------------------------------------------------------------------------------------------------ integrated gradients

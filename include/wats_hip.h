@@ -965,6 +965,57 @@ int wg_trial_logits(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t
                     float* out, void* stream);
 
 /* ----------------------------------------------------------------------
+ * wg_fga_scores (csrc/fga.hip): what calib_fga.py:864-898 reads from one
+ * forward and up to three backward passes of the whole graph, for B targets
+ * in one call, on the two-layer base model and a unit canonical CSR.  Target b
+ * is targets[b] (int32, duplicates allowed) with the toggle set S_b =
+ * tog_ids[tog_ptr[b] .. tog_ptr[b + 1]) (ascending, distinct, never t), as
+ * wg_target_logits has it: N'(t) = N(t) delta S_b, N'(j) = N(j) delta {t} for
+ * j in S_b, deg' = |N'| (0 -> 1, a constant then).  z = x W1^T and
+ * h = relu(A_hat z + b1) of the BASE graph are (n, Hd) float32 arguments.
+ * g_logits (B, G, C) float32 holds d L / d out_t for G in {1, 3} scalars L per
+ * target: row 0 the loss, rows 1 and 2 p_max and p_smax.  Per gradient row,
+ * with q = W2^T g, m_i = q * [y1_i + b1 > 0] (strictly) and a_tt = [t in N'(t)]:
+ *   grow_j = (q . h_j - q . y2) / deg_t + (a_tt / deg_t^2) m_t . (z_j - y1_t)
+ *   gcol_i = [i in N'(t)] (1 / (deg_t deg_i)) m_i . (z_t - y1_i)
+ * the entries d / d A[t, j] and d / d A[i, t] of the target probe's layout.
+ * For the local j (N(t) + S_b) y1_j, h_j, deg_j, y2 and y1_t are summed in
+ * float64 from z on the flipped rows, every row by the whole workgroup (wave w
+ * takes the entries w, w + 4, ..., the waves' sums are added in wave order,
+ * which is how wg_target_logits shares its long rows); every other j reads
+ * the float32 h_j and has gcol_j = +0.  Every sum and product is float64 in an
+ * order fixed by the rows, Hd and the launch shape; grow_j and gcol_j are each
+ * rounded once to float32.  The entry (t, t) is one variable: its score is -10
+ * and its two gradient slots are not defined.
+ * From those rounded values, in float32 and operation for operation,
+ * wg_flip_select's score: a_j from the base row and S_b, s_j = (grow_j +
+ * gcol_j) d_j, the rerank (row half only) for the targets with rerank[b] != 0
+ * (int32 [B], nullable, read only with G == 3; p_top2 (B, 2) float32 then),
+ * s_t = -10, and the best topk (1 .. 8) per target under wg_flip_select's total
+ * order.  Outputs: best_ids (B, topk) int32, best_scores (B, topk); optional
+ * (NULL: none) grads (B, G, 2 n) and scores (B, n).  n_workgroups = 0 picks the
+ * grid of the pass over j (ceil(n / 64), at most 512), 1 .. 512 force it; the
+ * result does not depend on it.  local_cap: the capacity of the local lists,
+ * at least the sum over the targets of |N(t)| + |S_b| (an entry past it is
+ * dropped, never written: that target's scores are then wrong and the call
+ * still returns WG_OK, as nothing on the host knows the rows' lengths; the
+ * bounds-checked variant traps with the target and the shortfall).  workspace: wg_fga_scores_workspace(n, Hd, B, G,
+ * local_cap, &bytes), 16-byte aligned: the coefficients, the local lists and
+ * the partial top-k lists.  No float atomics: the same input gives the same
+ * bits.  Asynchronous, no allocation, capturable.  1 <= Hd, C <= 256; n,
+ * nnz or local_cap above int32, or B above 2^20: WG_ERR_UNSUPPORTED.  Every argument is checked before any
+ * device call, ids on the device in the bounds-checked variant only.
+ * ---------------------------------------------------------------------- */
+int wg_fga_scores_workspace(int64_t n, int64_t Hd, int64_t B, int32_t G, int64_t local_cap,
+                            int64_t* bytes);
+int wg_fga_scores(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices, int64_t Hd,
+                  const float* z, const float* h, const float* b1, const float* W2, int64_t C,
+                  int64_t B, const int32_t* targets, const int32_t* tog_ptr, const int32_t* tog_ids,
+                  int32_t G, const float* g_logits, const int32_t* rerank, const float* p_top2,
+                  int32_t topk, int32_t n_workgroups, int64_t local_cap, void* workspace,
+                  float* grads, float* scores, int32_t* best_ids, float* best_scores, void* stream);
+
+/* ----------------------------------------------------------------------
  * The integrated-gradient scores of calib_attack/calib_iga.py on the sparse
  * path (csrc/iga.hip), for the two-layer base model (src/gnn/model.py:37-53,
  * eval mode) on a unit (value-free) canonical CSR.  z = x W1^T and
