@@ -33,7 +33,9 @@ Calib_Random / Calib_RND / trial_logits (the reference's random baseline attacks
 the reference's own random stream and evaluated by one HIP launch, several targets in lock step),
 TemperatureScaling / VectorScaling / MatrixScaling / ETS / scaled_log_probs / train_scaling (the node-wise calibrators:
 their row maps fused in HIP, a training epoch -- loss, gradients, Adam, early stopping -- in one launch on a device
-state block).
+state block), calibration_report / CalibrationReport / evaluate_calibration / evaluate_calibration_probs /
+reliability_curves / average_ece_many (the harness's evaluation step: accuracy, confidence, per-class and top-label
+ECE, NLL, Brier and the reliability curves from one fused HIP binning pass and one host read).
 """
 from ._lib import LIB_PATH, WaveletError  # noqa: F401
 from .graphgen import CSRGraph, named_graph, rmat_graph  # noqa: F401
@@ -132,6 +134,16 @@ from .scaling import (  # noqa: F401
     ets_label_probs,
     scaled_log_probs,
     train_scaling,
+)
+from .metrics import (  # noqa: F401
+    CalibrationReport,
+    average_ece_many,
+    calculate_average_ece,
+    calculate_ece,
+    calibration_report,
+    evaluate_calibration,
+    evaluate_calibration_probs,
+    reliability_curves,
 )
 
 __version__ = "0.1.0"

@@ -125,6 +125,14 @@ SIGNATURES = {
     "wg_scale_epoch": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32,
                                       c_vp]),
     "wg_ets_label_probs": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_vp] * 6 + [c_vp]),
+    "wg_calib_chunk_rows": (ctypes.c_int, []),
+    "wg_calib_max_rows": (ctypes.c_int, []),
+    "wg_calib_max_classes": (ctypes.c_int, []),
+    "wg_calib_max_bins": (ctypes.c_int, []),
+    "wg_calib_workspace": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_calib_bins": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                     c_vp, c_vp]),
+    "wg_calib_ece": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "wg_csr_transpose_map": (ctypes.c_int, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wg_bfs_levels": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "wg_gat_long_row": (ctypes.c_int, []),

@@ -1185,6 +1185,89 @@ int wg_ets_label_probs(int64_t n_total, int64_t n_rows, int64_t C, const float* 
                        const int32_t* rows, const int64_t* labels, const float* temperature,
                        double* p0y, double* p1y, void* stream);
 
+/* -------------------------------------------------------------------------
+ * Section 8(f): the evaluation the harness runs after every calibrator and
+ * every attack (csrc/calib.hip).  Replaces the host loops of
+ * evaluate_calibration / evaluate_calibration_probs
+ * (benchmark_calibration_methods.py:87-158), evaluate_model_calibration
+ * (ugca_calib_attack.py:78-104), calculate_ece / calculate_average_ece
+ * (utils/ece.py:8-89) and the binning of sklearn's calibration_curve that
+ * ece_chart / draw_multiple_ece_charts plot (utils/ece.py:109-115, :191-197,
+ * :249-251).
+ *
+ * wg_calib_bins: G sets of outputs out (G, n, C) float32 share labels
+ * (n) int64 and the row list rows (n_rows) int64, any order, a row listed
+ * twice counts twice (probs[idx]); NULL means all rows in order (then n_rows
+ * == n).  A row id outside [0, n) is never read: it is counted in scalars[7]
+ * (in every build).  kind says what out holds, per element:
+ *   WG_CALIB_PROBS   p = the float32 as given
+ *   WG_CALIB_EXP     p = (float)exp((double)x), not normalised: what the
+ *                    harness does to whatever a model returns
+ *                    (benchmark_calibration_methods.py:102-103), so p may
+ *                    exceed 1
+ *   WG_CALIB_LOGITS  p = the float64 softmax of the row, rounded once
+ * (double)p is compared with edges (n_bins + 1) float64, ascending, on the
+ * device, exactly as np.digitize(p, edges, right=True) - 1 (utils/ece.py:
+ * 39-40): bin b holds edges[b] < p <= edges[b + 1].  The caller passes
+ * np.linspace(0, 1, n_bins + 1); the kernel never recomputes an edge.
+ *
+ * table (G, C + 1, n_bins + 2, 3) uint64.  Cell (g, c, b) of a bin b <
+ * n_bins: the count, the count of those rows whose label is c, and sum p in
+ * fixed point, p added as (uint64)rint((double)p * 2^40) (exact for a float32
+ * p >= 2^-17, else within 2^-41; 2^23 rows stay below 2^63).  Slot n_bins
+ * holds p <= edges[0] (third word: the count of exact zeros), slot n_bins + 1
+ * everything else (p > edges[n_bins], NaN; third word: the count of NaN and
+ * +inf).  Slice c == C is the top-label table: p is the row's maximum (a NaN
+ * above every number), its label count the rows whose first maximal column
+ * is the label.  A label outside [0, C) belongs to no class.  sklearn's
+ * calibration_curve rule, searchsorted(edges[1:-1], p), differs on [0, 1]
+ * only in putting p == 0 into bin 0, so the same table serves it.  Integer
+ * sums commute: the table has the same bits for every grid and every run.
+ *
+ * scalars (G, 8) float64: [0] rows taken, [1] rows whose p are all finite,
+ * and over those [2] rows whose first maximal column is the label, [3] sum
+ * max p, [4] sum -log p_label (LOGITS: the float64 log-softmax, EXP:
+ * -x_label, PROBS: -log p; rows with 0 <= label < C and p_label > 0 only),
+ * [5] the rows [4] used, [6] sum_c (p_c - [label == c])^2; [7] row ids
+ * refused.  The sums are taken per chunk of wg_calib_chunk_rows() (256)
+ * consecutive entries of the row list, a chunk's partial a function of that
+ * chunk alone, the partials added in ascending chunk order (wg_scale_epoch's
+ * scheme): the same bits for every grid.  n_workgroups = 0 picks the grid
+ * (one workgroup per chunk, at most 1024), 1 .. 1024 force it.  workspace:
+ * wg_calib_workspace bytes, 8-byte aligned (the chunk partials).  A table
+ * of at most 5120 words is kept in LDS by each workgroup and added to the
+ * zeroed table with integer global adds at the end; a larger one is added to
+ * in place.
+ *
+ * wg_calib_ece (utils/ece.py:44-60 on every slice): bins with count <
+ * min_count (the reference: 4) are skipped, |sum p / cnt - sum y / cnt| *
+ * (cnt / n_rows) is added in ascending bin order in float64; ece_class
+ * (G, C), ece_top (G) the same sum on slice C.
+ *
+ * Limits: C <= wg_calib_max_classes() (256), n_bins <= wg_calib_max_bins()
+ * (64), n_rows <= wg_calib_max_rows() (2^23), G <= 4096: above them
+ * WG_ERR_UNSUPPORTED; a bad kind or shape, a NULL or misaligned pointer:
+ * WG_ERR_INVALID, all before any device call.  Both entries are asynchronous,
+ * allocate nothing, zero what they accumulate into, and use no float
+ * atomics.  n_rows == 0 or G == 0 is WG_OK with zeroed outputs.  The
+ * bounds-checked variant checks the bin index and the table cell on the
+ * device.
+ * ---------------------------------------------------------------------- */
+#define WG_CALIB_PROBS 0
+#define WG_CALIB_EXP 1
+#define WG_CALIB_LOGITS 2
+int wg_calib_chunk_rows(void);
+int wg_calib_max_rows(void);
+int wg_calib_max_classes(void);
+int wg_calib_max_bins(void);
+int wg_calib_workspace(int64_t G, int64_t C, int64_t n_bins, int64_t n_rows, int64_t* bytes);
+int wg_calib_bins(int64_t G, int64_t n, int64_t C, int32_t kind, const float* out,
+                  const int64_t* labels, int64_t n_rows, const int64_t* rows, int32_t n_bins,
+                  const double* edges, int32_t n_workgroups, void* workspace, uint64_t* table,
+                  double* scalars, void* stream);
+int wg_calib_ece(int64_t G, int64_t C, int32_t n_bins, int64_t n_rows, int32_t min_count,
+                 const uint64_t* table, double* ece_class, double* ece_top, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
