@@ -28,6 +28,9 @@ struct HeadArgs {
   const float* b2;  // [1]
 };
 
+// ReLU that hands a NaN on, as torch's does (fmaxf(NaN, 0) is 0: a NaN feature would leave a finite t)
+__device__ __forceinline__ float head_relu(float v) { return v > 0.0f ? v : (v == v ? 0.0f : v); }
+
 // lanes < hid: pre-activation of hidden unit `lane`; returns t (wave-uniform)
 __device__ __forceinline__ float head_mlp(const HeadArgs& a, int64_t row, int lane, float& pre) {
   pre = 0.0f;
@@ -38,7 +41,7 @@ __device__ __forceinline__ float head_mlp(const HeadArgs& a, int64_t row, int la
     const float* w = a.W1 + (int64_t)lane * a.F;
     for (int64_t f = 0; f < a.F; ++f) acc = fmaf(w[f], h[f], acc);
     pre = acc;
-    contrib = a.W2[lane] * fmaxf(acc, 0.0f);
+    contrib = a.W2[lane] * head_relu(acc);
   }
   for (int off = 32; off >= 1; off >>= 1) contrib += __shfl_xor(contrib, off, 64);  // same sum on every lane
   return contrib + a.b2[0];
@@ -108,9 +111,9 @@ __global__ __launch_bounds__(kBlock) void head_backward_kernel(HeadArgs a, const
     }
     dTs = wave_sum(dTs);
     const double dT = -(double)dTs / ((double)T * (double)T);
-    const double dt = dT * (double)et / ((double)et + 1.1);  // d log(e^t + 1.1) / dt
+    const double dt = dT * (double)et / ((double)et + (double)1.1f);  // d log(e^t + 1.1f) / dt: the forward's constant
     if (lane < a.hid) {
-      const float z = fmaxf(pre, 0.0f);
+      const float z = head_relu(pre);
       mine[(int64_t)a.hid * a.F + a.hid + lane] += dt * (double)z;        // gW2
       const double dz = (pre > 0.0f) ? dt * (double)a.W2[lane] : 0.0;
       mine[(int64_t)a.hid * a.F + lane] += dz;                             // gb1

@@ -7,6 +7,17 @@ NLL through it every epoch (:145-151).  :func:`wats_head` is that whole
 expression as two HIP kernels (``csrc/head.hip``): forward, and a backward
 giving the logits gradient and the four parameter gradients.  Float64 sums in a
 fixed order make the backward deterministic.
+
+Non-finite values (``tests/test_head_precision.py``).  A row is computed from
+its own row of ``H`` and ``logits`` alone, so a NaN in one row leaves every
+other row of the output and of the logits gradient bitwise as it is without it.
+The row itself becomes NaN in both (the ReLU hands a NaN on, as torch's does),
+and ``g_W2`` and ``g_b2`` become NaN.  Where ``net(H) > 88.8``, ``exp`` is inf
+in float32 and so is ``T``: that row of the output is finite and constant,
+``-log(C)``, and its row of the logits gradient is 0, but ``d T / d net`` is
+``inf / inf``, so the parameter gradients are NaN in the places where torch's
+float32 expression has them NaN (``g_b2``, all of ``g_W2``, and the ``g_b1`` /
+``g_W1`` rows of the hidden units active on that row).
 """
 from __future__ import annotations
 
