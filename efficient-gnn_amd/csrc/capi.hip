@@ -228,6 +228,8 @@ int wg_laplacian_tune(wg_laplacian_t L, const char* key, int64_t value) {
   } else if (!strcmp(key, "team_spec")) {
     L->tune.team_spec = value ? 1 : 0;
     return WG_OK;  // launch-time choice
+  } else if (!strcmp(key, "ids16")) {
+    L->tune.ids16 = value ? 1 : 0;  // plan-time choice (the wave tables carry the 16-bit turn counts)
   } else if (!strcmp(key, "team_tail")) {
     if (value < 0) return fail(WG_ERR_INVALID, "team_tail must be >= 0");
     L->tune.team_tail = value;
@@ -332,6 +334,11 @@ const char* wg_laplacian_describe(wg_laplacian_t L, int64_t F) {
     snprintf(buf, sizeof(buf), "team: waves=%d long_rows=%d part_slots=%d max_parts=%d npot_rows=%d spec=%d pending_arrivals=%d\n",
              p->team.n_waves, p->team.n_long, p->team.n_slots, p->team.max_parts, p->team.npot_rows, L->tune.team_spec,
              pending(p->team.warr, p->team.n_long));
+    g_text += buf;
+    // the straight-line kernels' 16-bit ids: converted turns out of all full turns, bytes of both id arrays
+    snprintf(buf, sizeof(buf), "ids16: on=%d turns16=%lld turns=%lld ids16_bytes=%lld ids32_bytes=%lld\n", L->tune.ids16,
+             (long long)p->team.turns16, (long long)p->team.turns, (long long)(16 * p->team.n_ids16),
+             (long long)(16 * p->team.n_sell));
     g_text += buf;
   }
   if (p->arrivals && p->n_split > 0) {

@@ -102,6 +102,9 @@ struct TeamPlan {
   int64_t n_rows = 0;        // rows of the table ([0, n_rows): the debug variant checks descriptors against it)
   int4* sell0 = nullptr;     // device [n_sell]: sell with caller-row ids (the folded chain's first launch)
   double* sdinv = nullptr;   // device [4 n_sell]: dinv of each id slot of sell (0 for pads)
+  int4* ids16 = nullptr;     // device [n_ids16]: 16-bit ids of the waves' leading all-low turns (plan_host.h
+                             // TeamIds16; the straight-line kernels read it), null where none is converted
+  int64_t n_ids16 = 0, turns16 = 0, turns = 0;  // its chunks; converted turns out of all full turns
   void release();
 };
 
@@ -275,6 +278,8 @@ struct Tuning {
                              // instead of Clenshaw's 3; 0 = Clenshaw
   int32_t team_spec = 1;     // team.hip: the Clenshaw-u chain's launches on straight-line kernels, one per chain
                              // mode (team_dev.h team_wave_spec); 0 = the generic kernel for every launch
+  int32_t ids16 = 1;         // team.hip: those kernels read a wave's leading all-low turns as 16-bit ids (one
+                             // id load per turn instead of two; plan_host.h TeamIds16); plan-time
   int32_t fold = 1;          // wg_wavelet_features on the team kernel: no permute-in pass (the first launch
                              // gathers the caller's X0 scaled by dinv, writes the internal X0, finishes
                              // the closed-form rows; team.hip cheb_team4_first_kernel); 2 = a pass writes
@@ -495,7 +500,7 @@ int build_pcol(wg_laplacian_s* L);
 // team.hip: the wave table of rows [0, n) for LF-lane sub-groups, and its launch
 // (dcol: the operator's column ids, or the hybrid step's tail-first copy, drsplit its rows' tail ends)
 int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32_t* dcol,
-                     const int32_t* drsplit, int order, TeamPlan* tp);
+                     const int32_t* drsplit, int order, bool ids16, TeamPlan* tp);
 struct StepArgs;
 // spec: the chain's own launches on their straight-line kernels (tuning key team_spec)
 int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, int spec, hipStream_t stream,

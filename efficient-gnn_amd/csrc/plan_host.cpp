@@ -164,6 +164,51 @@ int plan_team_waves(const std::vector<int32_t>& rs, const std::vector<int32_t>& 
   return WG_OK;
 }
 
+// 16-bit ids of the waves' leading all-low full turns (plan_host.h TeamIds16): columns are sorted in a
+// row and rows numbered by descending length, so the ids past 65534 are a row's last entries and a
+// wave's leading turns are low
+int plan_team_ids16(TeamWaves* w, int LF, TeamIds16* out) {
+  if (LF < 1 || LF > 64 || (w->wd.size() & 1)) return fail(WG_ERR_INVALID, "team ids16: LF %d, %zu descriptors", LF, w->wd.size());
+  const size_t G = (size_t)(64 / LF);
+  const std::vector<int4>& sell = w->sell;
+  out->ids.clear();
+  out->turns16 = out->turns = 0;
+  auto low = [](const int4& c) {
+    const int32_t* id = &c.x;
+    for (int i = 0; i < 4; ++i)
+      if (id[i] != kPadCol && (id[i] < 0 || id[i] >= (int32_t)kIds16Pad)) return false;
+    return true;
+  };
+  auto half = [](int32_t id) -> uint32_t { return id == kPadCol ? kIds16Pad : (uint32_t)id; };
+  auto pack = [&](const int4& a, const int4& b) {
+    return int4{(int32_t)(half(a.x) | half(a.y) << 16), (int32_t)(half(a.z) | half(a.w) << 16),
+                (int32_t)(half(b.x) | half(b.y) << 16), (int32_t)(half(b.z) | half(b.w) << 16)};
+  };
+  for (size_t i = 0; i < w->wd.size(); i += 2) {
+    int4& d0 = w->wd[i];
+    if (d0.x < 0 || d0.y < 0 || (size_t)d0.x + (size_t)d0.y * G > sell.size() || ((uint32_t)d0.w >> kIds16Shift))
+      return fail(WG_ERR_INVALID, "team ids16: wave %zu: descriptor {%d, %d, %d, %#x}", i / 2, d0.x, d0.y, d0.z, d0.w);
+    const size_t x = (size_t)d0.x;
+    const int full = std::min(d0.y >> 1, kIds16Max);
+    int n16 = 0;
+    for (; n16 < full; ++n16) {
+      bool ok = true;
+      for (size_t c = x + 2 * (size_t)n16 * G; ok && c < x + 2 * (size_t)(n16 + 1) * G; ++c) ok = low(sell[c]);
+      if (!ok) break;
+    }
+    out->turns += d0.y >> 1;
+    out->turns16 += n16;
+    if (!n16) continue;
+    if (out->ids.empty()) out->ids.assign((sell.size() + 1) / 2, int4{-1, -1, -1, -1});
+    const size_t b = ids16_base((uint32_t)x);
+    for (size_t t = 0; t < (size_t)n16; ++t)
+      for (size_t sg = 0; sg < G; ++sg)
+        out->ids[b + t * G + sg] = pack(sell[x + 2 * t * G + sg], sell[x + (2 * t + 1) * G + sg]);
+    d0.w |= (int32_t)((uint32_t)n16 << kIds16Shift);
+  }
+  return WG_OK;
+}
+
 // smallest divisor of G that is >= want (G itself if none smaller)
 int divisor_at_least(int G, int64_t want) {
   for (int d = 1; d <= G; ++d)

@@ -61,6 +61,23 @@ struct TeamWaves {
 int plan_team_waves(const std::vector<int32_t>& rs, const std::vector<int32_t>& re, const std::vector<int32_t>& col,
                     int LF, int iter, int order, TeamWaves* out);
 
+// team.hip: 16-bit column ids for a wave's leading full turns whose real ids are all <= 65534
+// (team_dev.h team_wave_spec).  n16, the count of such turns, goes into bits
+// kIds16Shift and up of the wave's d0.w; turn t < n16 of sub-group sg is the one 16-B chunk
+// ids[ids16_base(d0.x) + t G + sg], the turn's eight ids in the slot order {c0.x .. c0.w, c1.x .. c1.w}
+// (slot s in half s & 1 of word s >> 1), pads kIds16Pad.  sell is left as it is.  The base needs no
+// descriptor field: a wave's ny G chunks of sell leave room for its <= ny / 2 turns of G chunks at
+// half its own offset, rounded up.  ids stays empty when no wave has such a turn.
+constexpr uint32_t kIds16Pad = 0xFFFF;
+constexpr int kIds16Shift = 17;
+constexpr int kIds16Max = (1 << 14) - 1;  // d0.w bits 17 .. 30
+constexpr uint32_t ids16_base(uint32_t first_chunk) { return (first_chunk + 1u) >> 1; }
+struct TeamIds16 {
+  std::vector<int4> ids;
+  int64_t turns16 = 0, turns = 0;  // converted turns; full turns of all waves
+};
+int plan_team_ids16(TeamWaves* w, int LF, TeamIds16* out);
+
 // team.hip: the folded chain's first-launch ids (caller rows) and each id slot's dinv; sell (the wave
 // table's ids) is moved in and mapped in place
 struct TeamFirstIds {

@@ -784,11 +784,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_of(const T* p, uint32_t by
 // chunk, the look-ahead of the last turn): wave-uniform branches around the loads, whose registers
 // start as zeros, not as copies of loaded ones (a copy would wait for its source).
 // once(): called one time, after the first turn's gathers are issued (work that hides behind them);
-// never when there is no turn (ny == 0).
-template <class Once>
+// never when there is no turn (ny == 0), nor when `pending` comes in false (accumulate_sell16_from ran
+// the wave's first turn).
+// AHEAD false (the 32-bit rest behind a wave's 16-bit turns): the next turn's ids are issued behind this
+// turn's gathers, not in front of them, so only one turn's ids are live at a time (they still return
+// behind the gathers, ahead of the sums' end)
+template <bool AHEAD = true, class Once>
 __device__ __forceinline__ void accumulate_sell_from(const StepArgs& a, u32x4_t c0, u32x4_t c1, uint32_t off,
                                                      uint32_t cstep, int ny, int fs, bool on, double (&acc)[4],
-                                                     Once&& once) {
+                                                     bool pending, Once&& once) {
   const __amdgpu_buffer_rsrc_t rs = buf_of(a.xm1, a.u_bytes);
   const __amdgpu_buffer_rsrc_t ri = buf_of(a.sell, 0x7fffffffu);
   const uint32_t rb = (uint32_t)a.ld * 4u;
@@ -799,17 +803,22 @@ __device__ __forceinline__ void accumulate_sell_from(const StepArgs& a, u32x4_t 
   auto gather = [&](uint32_t c) -> u32x4_t {
     return __builtin_amdgcn_raw_buffer_load_b128(rs, __umul24(c, rb) + lo, 0, 0);
   };
-  bool pending = true;
   const int pairs = ny >> 1;
   for (int t = 0; t < pairs; ++t) {
     off += 2 * cstep;
     u32x4_t n0 = {0u, 0u, 0u, 0u}, n1 = n0;  // (a turn that does not exist reads neither)
-    if (2 * t + 2 < ny) n0 = ld(off);
-    if (2 * t + 3 < ny) n1 = ld(off + cstep);
+    if constexpr (AHEAD) {
+      if (2 * t + 2 < ny) n0 = ld(off);
+      if (2 * t + 3 < ny) n1 = ld(off + cstep);
+    }
     const uint32_t cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
     u32x4_t x[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) x[u] = gather(cc[u]);
+    if constexpr (!AHEAD) {
+      if (2 * t + 2 < ny) n0 = ld(off);
+      if (2 * t + 3 < ny) n1 = ld(off + cstep);
+    }
     if (pending) {
       once();
       pending = false;
@@ -826,6 +835,61 @@ __device__ __forceinline__ void accumulate_sell_from(const StepArgs& a, u32x4_t 
     if (pending) once();
     sum_turn(x, 4, acc);
   }
+}
+
+// The wave's n16 >= 1 leading turns on 16-bit ids (plan_host.h TeamIds16), in front
+// of accumulate_sell_from on the rest: one 16-B id load per turn, h the first turn's (in flight, at byte
+// offset off16 of ids16), the same eight gathers in the same slot order and the same sum_turn, so the
+// sums keep their bits.  The pad 0xFFFF must cost no request, as kPadCol: the gathers go through a
+// resource that ends at 65535 rows at the latest, and 65535 rb + fs 16 < 2^27 does not wrap back into
+// it; a real id is <= 65534 and inside both ends.  A lane that is off reads ids 0 at kOobOff.
+// The last of these turns issues the first 32-bit turn's chunks (c0, c1: zeros where the sub-group has
+// no such chunk; rem chunks at byte offset off of a.sell) in the place of its look-ahead.  A turn's
+// look-ahead is issued behind its gathers: one turn's ids live at a time, and the gathers' wait does not
+// stand behind a cold id line.
+// once(): after the first turn's gathers, as in accumulate_sell_from.
+template <class Once>
+__device__ __forceinline__ void accumulate_sell16_from(const StepArgs& a, const int4* ids16, u32x4_t h, uint32_t off16,
+                                                       int n16, u32x4_t& c0, u32x4_t& c1, uint32_t off, int rem,
+                                                       uint32_t cstep, int fs, bool on, double (&acc)[4],
+                                                       Once&& once) {
+  // (readfirstlane: both are launch-uniform; the row bytes and the resource stay in scalar registers)
+  const uint32_t rb = __builtin_amdgcn_readfirstlane((uint32_t)a.ld * 4u);
+  const uint32_t low_bytes = __builtin_amdgcn_readfirstlane(
+      a.u_bytes < (uint32_t)kIds16Pad * rb ? a.u_bytes : (uint32_t)kIds16Pad * rb);
+  const __amdgpu_buffer_rsrc_t rs = buf_of(a.xm1, low_bytes);
+  const __amdgpu_buffer_rsrc_t ri = buf_of(a.sell, 0x7fffffffu);
+  const __amdgpu_buffer_rsrc_t rh = buf_of(ids16, 0x7fffffffu);
+  const uint32_t lo = on ? (uint32_t)fs * 16u : kOobOff;
+  auto gather8 = [&](const u32x4_t& q, u32x4_t* x) {
+    const uint32_t cc[8] = {q.x & 0xffffu, q.x >> 16, q.y & 0xffffu, q.y >> 16,
+                            q.z & 0xffffu, q.z >> 16, q.w & 0xffffu, q.w >> 16};
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, __umul24(cc[u], rb) + lo, 0, 0);
+  };
+  bool pending = true;
+  u32x4_t x[8];
+  for (int t = 0; t + 1 < n16; ++t) {
+    off16 += cstep;
+    gather8(h, x);
+    const u32x4_t nh = __builtin_amdgcn_raw_buffer_load_b128(rh, on ? off16 : kOobOff, 0, (int)(1u << 31));
+    if (pending) {
+      once();
+      // (the empty statement keeps this branch when once() is empty, and with it the loop's first turn
+      // peeled: its wait is then for the ids alone, not the loop head's vmcnt(0), which would take in the
+      // epilogue operands)
+      asm volatile("");
+      pending = false;
+    }
+    sum_turn(x, 8, acc);
+    h = nh;
+  }
+  gather8(h, x);
+  c0 = c1 = u32x4_t{0u, 0u, 0u, 0u};  // (defined here, not carried through the loop)
+  if (rem > 0) c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, on ? off : kOobOff, 0, (int)(1u << 31));
+  if (rem > 1) c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, on ? off + cstep : kOobOff, 0, (int)(1u << 31));
+  if (pending) once();
+  sum_turn(x, 8, acc);
 }
 
 template <int VEC, bool BCAST, bool HOT>

@@ -57,7 +57,8 @@ __global__ __launch_bounds__(256, 6) void cheb_team4_spec_kernel(TeamArgs t) {
 }  // namespace
 
 void TeamPlan::release() {
-  for (void* q : {(void*)wd, (void*)sell, (void*)wpart, (void*)warr, (void*)sell0, (void*)sdinv}) (void)hipFree(q);
+  for (void* q : {(void*)wd, (void*)sell, (void*)wpart, (void*)warr, (void*)sell0, (void*)sdinv, (void*)ids16})
+    (void)hipFree(q);
   *this = TeamPlan{};
 }
 
@@ -82,12 +83,22 @@ int build_team_first(wg_laplacian_s* L, TeamPlan* tp) {
 
 // The wave table and SELL ids of the rows [0, n) of L's operator for LF-lane sub-groups
 // (plan_team_waves), with the long rows' partials and arrival counters
+// ids16: also the 16-bit ids of the waves' leading all-low turns (plan_team_ids16): only where the
+// gathered columns are the rows' own numbering (no hybrid tail, shard or literal operator)
 int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32_t* dcol,
-                     const int32_t* drsplit, int order, TeamPlan* tp) {
+                     const int32_t* drsplit, int order, bool ids16, TeamPlan* tp) {
   std::vector<int32_t> rs, col, re;  // the entries of row r are col[rs[r] .. re[r])
   if (int rc = download_csr(L, n, dcol, drsplit, &rs, &col, &re)) return rc;
   TeamWaves w;
   if (int rc = plan_team_waves(rs, re, col, LF, iter, order, &w)) return rc;
+  TeamIds16 h;
+  if (ids16)
+    if (int rc = plan_team_ids16(&w, LF, &h)) return rc;
+  if (h.ids.size() >= ((size_t)1 << 27)) return fail(WG_ERR_UNSUPPORTED, "team waves: 16-bit id array exceeds 2 GB");
+  tp->n_ids16 = (int64_t)h.ids.size();
+  tp->turns16 = h.turns16;
+  tp->turns = 0;
+  for (size_t i = 0; i < w.wd.size(); i += 2) tp->turns += w.wd[i].y >> 1;
   tp->max_parts = w.max_parts;
   tp->npot_rows = w.npot_rows;
   tp->n_waves = (int32_t)(w.wd.size() / 2);
@@ -99,6 +110,7 @@ int build_team_waves(wg_laplacian_s* L, int64_t n, int LF, int iter, const int32
   w.wd.resize(std::max<size_t>(w.wd.size(), 2), int4{0, 0, 0, 0});
   int rc = upload(&tp->wd, w.wd);
   if (!rc) rc = upload(&tp->sell, w.sell);
+  if (!rc && !h.ids.empty()) rc = upload(&tp->ids16, h.ids);
   if (!rc) rc = dmalloc(&tp->wpart, (size_t)std::max(w.n_slots, 1) * tp->width);
   if (!rc) rc = dmalloc(&tp->warr, (size_t)std::max(w.n_long, 1));
   if (!rc && dzero(tp->warr, sizeof(uint32_t) * std::max(w.n_long, 1)) != hipSuccess)
@@ -116,6 +128,7 @@ int launch_team4(const TeamPlan& tp, const StepArgs& a, int variant, int spec, h
   t.wpart = tp.wpart;
   t.warr = tp.warr;
   t.a.sell = tp.sell;
+  t.ids16 = tp.ids16;
   team_args_debug(t, tp);
   if (first) {  // the folded chain's first launch
     const bool gx = first->gather_x0;

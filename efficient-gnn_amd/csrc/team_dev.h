@@ -9,11 +9,13 @@ namespace wg {
 namespace {
 
 // wave descriptor (two int4 per wave):
-//   d0 = {first SELL chunk, chunks per sub-group, first row, LN | rows << 8 | part << 16}
+//   d0 = {first SELL chunk, chunks per sub-group, first row, LN | rows << 8 | part << 16 | n16 << 17}
+//        (n16: leading turns also held as 16-bit ids, plan_host.h TeamIds16; team_wave_spec alone reads it)
 //   d1 = {part index, parts of the row, first partial slot, arrival counter}   (part waves only)
 struct TeamArgs {
   StepArgs a;
   const int4* wd;
+  const int4* ids16;  // the 16-bit ids of turns [0, n16) of each wave (null: every n16 is 0)
   int32_t n_waves;
   double* wpart;   // [slots][LF * 4] float64 partials of part waves
   uint32_t* warr;  // [long rows] arrival counters (0 between launches: the last arrival resets)
@@ -289,10 +291,12 @@ __device__ __forceinline__ void epilogue_spec(const StepArgs& a, int row, int fs
 // the one the gathers need); the gather loop, a step's 1 / dinv computed behind the first turn's
 // gathers; the epilogue.  A long row's last arriver issues its first four parts' partials, then the
 // operands, before the first add (part order kept).
-template <class M>
-__device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
+// H16: the wave's first n16 >= 1 turns are on 16-bit ids (one chunk per turn: accumulate_sell16_from).
+// The two forms are whole paths of their own from the descriptor to the stores (team_wave_spec picks one
+// per wave), so no loaded register of one meets the other's at a join.
+template <class M, bool H16>
+__device__ __forceinline__ void team_wave_spec_on(const TeamArgs& t, int w, const int4 d0) {
   const StepArgs& a = t.a;
-  const int4 d0 = t.wd[2 * w];  // uniform address: a scalar load
   const int lane = threadIdx.x & 63;
   const int LF = a.LF;
   const int G = 64 / LF;
@@ -306,12 +310,18 @@ __device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
   const int row = d0.z + team;  // rows are 24-bit ids (gather4_applies)
   const bool active = sg < G && team < tpw;
   const int ny = d0.y;
+  const int n16 = (int)((uint32_t)d0.w >> kIds16Shift);  // leading turns on 16-bit ids (2 n16 <= ny)
   const uint32_t cstep = (uint32_t)G * 16u;
   const uint32_t off0 = ((uint32_t)d0.x + (uint32_t)sg) * 16u;
+  const uint32_t off16 = (ids16_base((uint32_t)d0.x) + (uint32_t)sg) * 16u;
   const __amdgpu_buffer_rsrc_t ri = buf_of(a.sell, 0x7fffffffu);
-  const u32x4_t c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, active && ny > 0 ? off0 : kOobOff, 0, (int)(1u << 31));
-  u32x4_t c1 = {0u, 0u, 0u, 0u};  // (a single-chunk wave does not read it)
-  if (ny > 1) c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, active ? off0 + cstep : kOobOff, 0, (int)(1u << 31));
+  u32x4_t h0 = {0u, 0u, 0u, 0u}, c0 = h0, c1 = h0;  // (a single-chunk wave does not read c1)
+  if constexpr (H16) {
+    h0 = __builtin_amdgcn_raw_buffer_load_b128(buf_of(t.ids16, 0x7fffffffu), active ? off16 : kOobOff, 0, (int)(1u << 31));
+  } else {
+    c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, active && ny > 0 ? off0 : kOobOff, 0, (int)(1u << 31));
+    if (ny > 1) c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, active ? off0 + cstep : kOobOff, 0, (int)(1u << 31));
+  }
   EpiRegs in;
   const bool own = active && ns == 0 && !part;
   epi_issue<M>(a, row, fs, own, in);
@@ -325,11 +335,15 @@ __device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
   };
   // behind the first turn's gathers: a step's 1 / dinv (the final launch has no registers to hold it
   // across the loop within 80)
-  constexpr bool kDivEarly = M::kPrev && M::kClen == 1;
+  // (nor has the 16-bit path of a step: there the division goes behind the loop too)
+  constexpr bool kDivEarly = M::kPrev && M::kClen == 1 && !H16;
   auto behind = [&] {
     if constexpr (kDivEarly) rinv = divide(in);
   };
-  accumulate_sell_from(a, c0, c1, off0, cstep, ny, fs, active, acc, behind);  // every lane
+  const uint32_t off32 = off0 + (uint32_t)(2 * n16) * cstep;  // the chunks behind the 16-bit turns
+  if constexpr (H16)
+    accumulate_sell16_from(a, t.ids16, h0, off16, n16, c0, c1, off32, ny - 2 * n16, cstep, fs, active, acc, behind);
+  accumulate_sell_from<!H16>(a, c0, c1, off32, cstep, ny - 2 * n16, fs, active, acc, !H16, behind);  // every lane
   if (ny <= 0) behind();  // no turn to hide it behind
   if constexpr (M::kPrev && !kDivEarly) rinv = divide(in);
   reduce_subgroups<4>(acc, LN, LF, team * LN * LF, fs);  // every lane (shuffles)
@@ -387,6 +401,13 @@ __device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
     }
     epilogue_spec<M>(a, row, lane, s, lin, M::kPrev ? divide(lin) : 0.0, 0);
   }
+}
+
+template <class M>
+__device__ __forceinline__ void team_wave_spec(const TeamArgs& t, int w) {
+  const int4 d0 = t.wd[2 * w];  // uniform address: a scalar load
+  if (((uint32_t)d0.w >> kIds16Shift) > 0) team_wave_spec_on<M, true>(t, w, d0);
+  else team_wave_spec_on<M, false>(t, w, d0);
 }
 
 }  // namespace
