@@ -339,9 +339,9 @@ int wg_calib_bins(int64_t G, int64_t n, int64_t C, int32_t kind, const float* ou
     return fail(WG_ERR_INVALID, "%s: a NULL or misaligned pointer with %lld rows", who, (long long)n_rows);
   hipStream_t stream = as_stream(stream_);
   const int64_t cells = table_cells(C, n_bins);
-  WG_HIP_TRY(hipMemsetAsync(table, 0, (size_t)(G * cells) * sizeof(uint64_t), stream));
+  WG_HIP_TRY(zero_async(table, (size_t)(G * cells) * sizeof(uint64_t), stream));
   if (n_rows == 0) {
-    WG_HIP_TRY(hipMemsetAsync(scalars, 0, (size_t)(G * kNS) * sizeof(double), stream));
+    WG_HIP_TRY(zero_async(scalars, (size_t)(G * kNS) * sizeof(double), stream));
     return WG_OK;
   }
   const int64_t n_chunks = n_chunks_of(n_rows);
@@ -377,8 +377,8 @@ int wg_calib_ece(int64_t G, int64_t C, int32_t n_bins, int64_t n_rows, int32_t m
     return fail(WG_ERR_INVALID, "%s: ece_class / ece_top NULL or not 8-byte aligned", who);
   hipStream_t stream = as_stream(stream_);
   if (n_rows == 0) {
-    WG_HIP_TRY(hipMemsetAsync(ece_class, 0, (size_t)(G * C) * sizeof(double), stream));
-    WG_HIP_TRY(hipMemsetAsync(ece_top, 0, (size_t)G * sizeof(double), stream));
+    WG_HIP_TRY(zero_async(ece_class, (size_t)(G * C) * sizeof(double), stream));
+    WG_HIP_TRY(zero_async(ece_top, (size_t)G * sizeof(double), stream));
     return WG_OK;
   }
   if (!table || !aligned8(table)) return fail(WG_ERR_INVALID, "%s: table NULL or not 8-byte aligned", who);

@@ -763,13 +763,13 @@ int wg_edge_mlp_backward(int64_t n, int64_t nnz, const int64_t* indptr, const in
   hipStream_t stream = as_stream(stream_);
   const MlpShape s = shape_of(C);
   if (!live) {   // zero gradients
-    WG_HIP_TRY(hipMemsetAsync(gW1, 0, sizeof(float) * 8 * C * C, stream));
-    WG_HIP_TRY(hipMemsetAsync(gb1, 0, sizeof(float) * 4 * C, stream));
-    WG_HIP_TRY(hipMemsetAsync(gW2, 0, sizeof(float) * 8 * C * C, stream));
-    WG_HIP_TRY(hipMemsetAsync(gb2, 0, sizeof(float) * 2 * C, stream));
-    WG_HIP_TRY(hipMemsetAsync(gw3, 0, sizeof(float) * 2 * C, stream));
-    WG_HIP_TRY(hipMemsetAsync(gb3, 0, sizeof(float), stream));
-    if (g_emb && n > 0) WG_HIP_TRY(hipMemsetAsync(g_emb, 0, sizeof(float) * n * C, stream));
+    WG_HIP_TRY(zero_async(gW1, sizeof(float) * 8 * C * C, stream));
+    WG_HIP_TRY(zero_async(gb1, sizeof(float) * 4 * C, stream));
+    WG_HIP_TRY(zero_async(gW2, sizeof(float) * 8 * C * C, stream));
+    WG_HIP_TRY(zero_async(gb2, sizeof(float) * 2 * C, stream));
+    WG_HIP_TRY(zero_async(gw3, sizeof(float) * 2 * C, stream));
+    WG_HIP_TRY(zero_async(gb3, sizeof(float), stream));
+    if (g_emb && n > 0) WG_HIP_TRY(zero_async(g_emb, sizeof(float) * n * C, stream));
     return WG_OK;
   }
   const MlpWs ws = carve(workspace, n, nnz, s);
@@ -780,8 +780,8 @@ int wg_edge_mlp_backward(int64_t n, int64_t nnz, const int64_t* indptr, const in
   hipLaunchKernelGGL(entry_rows_kernel, dim3((unsigned)ceil_div(nnz, kBlock)), dim3(kBlock), 0, stream, n, nnz, indptr,
                      ws.rows);
   WG_LAUNCH_CHECK();
-  WG_HIP_TRY(hipMemsetAsync(ws.partial, 0, sizeof(double) * s.P * G, stream));
-  if (gemb) WG_HIP_TRY(hipMemsetAsync(ws.gacc, 0, sizeof(double) * n * C, stream));
+  WG_HIP_TRY(zero_async(ws.partial, sizeof(double) * s.P * G, stream));
+  if (gemb) WG_HIP_TRY(zero_async(ws.gacc, sizeof(double) * n * C, stream));
   MlpArgs a{};
   a.n = n; a.nnz = nnz; a.C = (int)C;
   a.seg = ws.rows; a.other = indices; a.pos = nullptr; a.emb = emb;

@@ -198,7 +198,7 @@ int wg_wats_head_backward(int64_t n, int64_t F, int64_t C, int32_t hid, const fl
                        grad_logits, static_cast<double*>(workspace));
     WG_LAUNCH_CHECK();
   } else {
-    WG_HIP_TRY(hipMemsetAsync(workspace, 0, (size_t)nb * P * sizeof(double), stream));
+    WG_HIP_TRY(zero_async(workspace, (size_t)nb * P * sizeof(double), stream));
   }
   hipLaunchKernelGGL(head_reduce_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, stream, P, nb,
                      static_cast<const double*>(workspace), hid, F, gW1, gb1, gW2, gb2);

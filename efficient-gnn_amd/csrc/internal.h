@@ -52,6 +52,25 @@ constexpr int kBlock = 256;   // 4 waves of 64 lanes
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Zeroing inside the entry points that may be captured (include/wats_hip.h): a kernel of the library's own, not
+// hipMemsetAsync.  The first memset node of a captured graph left non-zero words behind on every replay after the first
+// (tests/test_streams.py: the binning table, the edge MLP's partials; tools/memset_node_probe.py shows it without this
+// library, profiles/r32/s1_memset_node_probe.log); a kernel node is replayed like every other launch.  Every caller's
+// pointer and size are multiples of 4 bytes; anything else is refused rather than handed to the runtime's memset.
+static __global__ __attribute__((unused)) void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+inline hipError_t zero_async(void* p, size_t bytes, hipStream_t stream) {
+  if (bytes == 0) return hipSuccess;
+  if ((reinterpret_cast<uintptr_t>(p) | bytes) & 3u) return hipErrorInvalidValue;
+  const size_t n = bytes / sizeof(uint32_t);
+  const size_t blocks = (n + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, stream,
+                     static_cast<uint32_t*>(p), n);
+  return hipGetLastError();
+}
+
 template <typename T>
 int dmalloc(T** p, size_t count) {
   *p = nullptr;

@@ -19,6 +19,12 @@
  *     All work is enqueued on it; no entry point synchronises the device
  *     except the ones documented as "synchronous" (graph creation / dense
  *     ingestion, which size device allocations from device-computed counts).
+ *     Entries documented as "may be captured" allocate nothing and read nothing
+ *     back, so they may run on a stream that is being captured into a graph and
+ *     re-zero whatever they accumulate into on every replay.  tests/stream_cases.py
+ *     classifies every entry that takes a stream by these words, and
+ *     tests/test_streams.py holds each to them: off the default stream, and from
+ *     a replayed graph whose inputs were rewritten.
  *   - Return value: WG_OK (0) or a negative WG_ERR_* code; the message of the
  *     last failure on the calling host thread is wg_last_error().  No entry
  *     point aborts the process.
@@ -98,6 +104,8 @@ int wg_dense_to_csr_fill(const float* adj, int64_t n_rows, int64_t n_cols, int64
  * colsum_f64[n_cols_global] and its diagonal into diag_f64 (indexed by the
  * global column id `row_offset + i` of local row i).  Column ids are global.
  * scipy semantics: `_laplacian.py:467` (w = m.sum(axis=0) - m.diagonal()).
+ * Asynchronous, allocates nothing, may be captured (float64 atomic adds: the
+ * order of a column's sum is not fixed).
  * ---------------------------------------------------------------------- */
 int wg_column_degree(int64_t n_rows, int64_t row_offset, const int64_t* indptr,
                      const int32_t* indices, const float* values /* NULL = 1 */,
@@ -129,7 +137,11 @@ int wg_laplacian_get_info(wg_laplacian_t L, wg_laplacian_info* info_host);
  * entries as CSR (int64 indptr[n_rows+1], int32 indices / float32 values
  * sized info.nnz; each row in ascending column order, or in the input's
  * order under WG_FLAG_KEEP_COLUMN_ORDER) plus iso[n_rows] (1 where
- * L_hat_ii = -1; nullable).  For bit-exact parity tests against scipy.  Async. */
+ * L_hat_ii = -1; nullable).  For bit-exact parity tests against scipy.
+ * Synchronous: temporary memory (the scan's scratch and, for a handle whose
+ * rows are sorted by internal column, two arrays of info.nnz entries) is
+ * allocated and freed inside the call, the work runs on `stream`, which is
+ * waited for before the temporaries are freed. */
 int wg_laplacian_export(wg_laplacian_t L, int64_t* indptr, int32_t* indices,
                         float* values, uint8_t* iso, void* stream);
 
@@ -147,7 +159,10 @@ int wg_operator_create(int64_t n, int64_t nnz, const int64_t* indptr, const int3
 /* -------------------------------------------------------------------------
  * a3: input signal.  Replaces `X0 = log1p(adj.sum(axis=1))`
  * (calibration/WATS.py:58-59): row sums INCLUDING self loops, float32 (N,1),
- * in the caller's row order.
+ * in the caller's row order.  One launch on `stream`, no allocation, no wait.
+ * Its only input is the handle, so a captured call has nothing a replay
+ * could follow: no capture test holds it (tests/stream_cases.py,
+ * ASYNC_REASONS) and no promise is made.
  * ---------------------------------------------------------------------- */
 int wg_log1p_degree(wg_laplacian_t L, float* x0, void* stream);
 
@@ -214,7 +229,8 @@ int wg_clenshaw_step(wg_laplacian_t L, int64_t F, const float* b1, const float* 
 
 /* Row permutation between the caller's order and the internal order:
  * direction 0: dst[i_internal] = src[perm[i]]  (caller -> internal)
- * direction 1: dst[perm[i]] = src[i_internal]  (internal -> caller). */
+ * direction 1: dst[perm[i]] = src[i_internal]  (internal -> caller).
+ * Asynchronous, allocates nothing, may be captured. */
 int wg_permute_rows(wg_laplacian_t L, int32_t direction, int64_t F, const float* src,
                     float* dst, void* stream);
 
@@ -296,15 +312,18 @@ int wg_profile_collect(wg_laplacian_t L, double* sum_ms_host, int64_t* launches_
  * launches.  Synchronous; resets the record like wg_profile_collect. */
 int wg_profile_durations(wg_laplacian_t L, double* ms_host, int64_t cap, int64_t* n_host);
 
-/* a6 standalone: H = S / (||S||_1,row + 1e-8) (calibration/WATS.py:71-72). */
+/* a6 standalone: H = S / (||S||_1,row + 1e-8) (calibration/WATS.py:71-72).
+ * Asynchronous, allocates nothing, may be captured. */
 int wg_row_l1_normalize(const float* S, float* H, int64_t n_rows, int64_t F, void* stream);
 
 /* Row-id mapping between the caller's numbering and the internal one:
- * direction 0: out[i] = internal id of caller row rows[i]; 1: the inverse. */
+ * direction 0: out[i] = internal id of caller row rows[i]; 1: the inverse.
+ * Asynchronous, allocates nothing, may be captured. */
 int wg_laplacian_map_rows(wg_laplacian_t L, int32_t direction, const int32_t* rows, int64_t n,
                           int32_t* out, void* stream);
 
-/* Multi-GPU halo pack: dst[i] = src[rows[i]] for i < n (row stride F). */
+/* Multi-GPU halo pack: dst[i] = src[rows[i]] for i < n (row stride F).
+ * Asynchronous, allocates nothing, may be captured. */
 int wg_gather_rows(const float* src, const int32_t* rows, int64_t n, int64_t F, float* dst,
                    void* stream);
 
@@ -380,6 +399,10 @@ int wg_dist_status(wg_dist_t D, int32_t* timed_out_host);
  * step kernel; WG_FLAG_TRANSPOSE builds adj_norm^T (the backward operator).
  * wg_spmm: y = op @ x for x, y (n, F) row-major in the caller's order, sums in
  * float64.  Handles are freed with wg_laplacian_destroy.  Create is synchronous.
+ * wg_spmm: the FIRST call with a given F on a handle built without
+ * WG_FLAG_NO_REORDER builds the plan and grows the handle's workspace
+ * synchronously (a stream sync, a device allocation); later calls at that width
+ * or a narrower one are asynchronous, allocate nothing and may be captured.
  * ---------------------------------------------------------------------- */
 int wg_rownorm_create(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* indices,
                       const float* values, uint32_t flags, void* stream, wg_laplacian_t* out);
@@ -517,6 +540,8 @@ int wg_coo_to_csr(int64_t n, int64_t n_edges, const void* src, const void* dst,
  * backward: from grad_out (n,C): grad_logits (nullable) and the parameter
  * gradients gW1 [hid][F], gb1, gW2, gb2 (overwritten, not accumulated), float64
  * sums in a fixed order; `workspace` holds wg_wats_head_workspace bytes.
+ * Forward and backward are asynchronous, allocate nothing, zero the workspace
+ * they accumulate into and may be captured.
  * ---------------------------------------------------------------------- */
 int wg_wats_head_forward(int64_t n, int64_t F, int64_t C, int32_t hid, const float* H,
                          const float* logits, const float* W1, const float* b1, const float* W2,
@@ -548,7 +573,7 @@ int wg_wats_head_backward(int64_t n, int64_t F, int64_t C, int32_t hid, const fl
  * 0 .. max_hop - 1 are ever assigned (bfs_depth = 2: the values are 0, 1 and the
  * maximum), and max_hop == 0 assigns none.  Self loops never change a level.
  * One launch per level; integer stores only, every writer of a cell writes the
- * same value.  Asynchronous, no allocation.
+ * same value.  Asynchronous, no allocation, may be captured.
  *
  * wg_gat_forward: CalibAttentionLayer.message / aggregation (GATS.py:134-167).
  * indptr / indices: the CSR by destination -- row i lists In(i), the sources j of
@@ -843,6 +868,8 @@ int wg_simcalib_backward(int64_t n, int64_t m, int64_t d, const float* x, const 
  * (DCGC.py:164-165): out[e] = 1 / (sqrt(sum_k (Q[rows[e]][k] - Q[cols[e]][k])^2)
  * + alpha), the sum in float64 over the differences themselves (rows[e] ==
  * cols[e] gives exactly (float)(1 / alpha)).  Q (n, C) float32.
+ * wg_edge_aggregate and wg_edge_pair_inv_distance are asynchronous, allocate
+ * nothing and may be captured.
  * ---------------------------------------------------------------------- */
 int wg_edge_mlp_max_c(void);
 int wg_edge_mlp_tile(void);
@@ -1158,7 +1185,9 @@ int wg_iga_scores(int64_t n, int64_t nnz, const int64_t* indptr, const int32_t* 
  * above the limit, sizes above int32: WG_ERR_UNSUPPORTED.  Row ids, labels
  * and the state's header are checked on the device in the bounds-checked
  * variant only.  n_rows == 0 is WG_OK with no launch (wg_scale_epoch:
- * WG_ERR_INVALID).  Asynchronous, allocate nothing.
+ * WG_ERR_INVALID).  Asynchronous, allocate nothing, may be captured: a replay
+ * of wg_scale_epoch is one more epoch on the state block (the last workgroup
+ * puts the arrival counter back), of wg_scale_state_init a fresh block.
  * ---------------------------------------------------------------------- */
 int wg_scale_max_c(int32_t mode);
 int wg_scale_chunk_rows(void);
@@ -1248,10 +1277,10 @@ int wg_ets_label_probs(int64_t n_total, int64_t n_rows, int64_t C, const float* 
  * (64), n_rows <= wg_calib_max_rows() (2^23), G <= 4096: above them
  * WG_ERR_UNSUPPORTED; a bad kind or shape, a NULL or misaligned pointer:
  * WG_ERR_INVALID, all before any device call.  Both entries are asynchronous,
- * allocate nothing, zero what they accumulate into, and use no float
- * atomics.  n_rows == 0 or G == 0 is WG_OK with zeroed outputs.  The
- * bounds-checked variant checks the bin index and the table cell on the
- * device.
+ * allocate nothing, use no float atomics and may be captured: each call, and
+ * so each replay, zeroes what it accumulates into.  n_rows == 0 or G == 0 is
+ * WG_OK with zeroed outputs.  The bounds-checked variant checks the bin index
+ * and the table cell on the device.
  * ---------------------------------------------------------------------- */
 #define WG_CALIB_PROBS 0
 #define WG_CALIB_EXP 1
