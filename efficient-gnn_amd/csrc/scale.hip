@@ -35,17 +35,17 @@
 #include <cstdint>
 
 #include "internal.h"
+#include "row_dev.h"
 
 namespace wg {
 namespace {
 
 constexpr int kTS = 0, kVS = 1, kMS = 2, kETS = 3;
-constexpr int kScaleMaxC = 256;     // four columns per lane
+constexpr int kScaleMaxC = kRowMaxC;   // four columns per lane (row_dev.h)
 constexpr int kScaleMaxCMS = 64;    // one lane per column, a column of dW in registers
 constexpr int kChunkRows = 256;     // listed rows per partial vector; 64 measured slower
 constexpr int kScaleWaves = kBlock / 64;
 constexpr int kMaxGrid = 1024;
-constexpr int kNQ = kScaleMaxC / 64;
 constexpr int kRedMax = 2 + kScaleMaxCMS * kScaleMaxCMS + kScaleMaxCMS;   // the longest partial vector (MS)
 
 // the state block of wg_scale_epoch, in 8-byte slots: slot 0 holds the arrival counter (uint32), the rest doubles
@@ -61,58 +61,6 @@ __host__ __device__ inline int64_t n_params(int mode, int64_t C) {
 // [0] loss, [1] correct, [2 ..) the parameter gradients in state order (MS: W row-major, then b; ETS: tau, w1..w3)
 __host__ __device__ inline int64_t partial_len(int mode, int64_t C) { return 2 + n_params(mode, C); }
 inline int64_t n_chunks_of(int64_t rows) { return ceil_div(rows, kChunkRows); }
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);   // the same sum on every lane
-  return v;
-}
-__device__ inline double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// the first index of the row's maximum, a NaN ranking above every number (torch.max, np.argmax)
-__device__ inline bool better(double a, int ia, double b, int ib) {
-  const bool na = a != a, nb = b != b;
-  if (na != nb) return na;
-  if (!na && a != b) return a > b;
-  return ia < ib;
-}
-__device__ inline int wave_argmax(const double (&v)[kNQ], int C, int lane) {
-  double bv = -INFINITY;
-  int bi = INT_MAX;
-#pragma unroll
-  for (int q = 0; q < kNQ; ++q) {
-    const int c = lane + 64 * q;
-    if (c < C && better(v[q], c, bv, bi)) bv = v[q], bi = c;
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double ov = __shfl_xor(bv, off, 64);
-    const int oi = __shfl_xor(bi, off, 64);
-    if (better(ov, oi, bv, bi)) bv = ov, bi = oi;
-  }
-  return bi;
-}
-
-// m and S = sum exp(v - m) over the row's columns; e[q] = exp(v[q] - m).  fmax drops a NaN, the sum brings it back.
-__device__ inline void row_exp(const double (&v)[kNQ], int C, int lane, double (&e)[kNQ], double* m, double* S) {
-  double mx = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < kNQ; ++q)
-    if (lane + 64 * q < C) mx = fmax(mx, v[q]);
-  mx = wave_max(mx);
-  double s = 0.0;
-#pragma unroll
-  for (int q = 0; q < kNQ; ++q) {
-    e[q] = lane + 64 * q < C ? exp(v[q] - mx) : 0.0;
-    s += e[q];
-  }
-  *m = mx;
-  *S = wave_sum(s);
-}
 
 // What a lane keeps of the parameters.  TS / VS: s and ds / d temperature of its columns; ETS: temp, its derivative
 // and the weights; MS: its bias (W is in LDS).
@@ -281,11 +229,6 @@ __device__ inline int64_t source_row(const PassArgs& a, int64_t r) {
   WG_DCHECK(i >= 0 && i < a.n_total, "scale: listed row %lld is %lld, outside [0, %lld)", (long long)r, (long long)i,
             (long long)a.n_total);
   return i;
-}
-
-__device__ inline void load_row(double (&z)[kNQ], const float* __restrict__ row, int C, int lane) {
-#pragma unroll
-  for (int q = 0; q < kNQ; ++q) z[q] = lane + 64 * q < C ? (double)row[lane + 64 * q] : 0.0;
 }
 
 // One chunk: rows [ch * kChunkRows, ...) of the list.  EPOCH: the gradient of the nll sum, the loss and the correct

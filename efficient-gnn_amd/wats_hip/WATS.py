@@ -18,6 +18,13 @@ features), ``wavelet_feats`` (precomputed features, e.g. a cache),
 ``fused_head`` (default off: the reference's torch ops; on: the temperature
 head + log_softmax as the fused HIP kernels of ``head.py``) and
 ``verbose``; ``fit()`` is an alias of ``calib_train``.
+
+Training extras (the defaults keep the reference's loop): ``epochs`` (250, WATS.py:146), ``train=False`` (construction
+stops before ``calib_train``, so that ``net`` can be loaded first), ``fused_training`` (each epoch of ``calib_train``
+-- the head on the calibration rows, NLL, accuracy, the four gradients, Adam, early stopping -- as one HIP launch on a
+device state block, ``head.train_wats_head``; the run is kept as ``training_run`` and ``verbose`` prints the
+reference's lines after the run, not during it) and, with it, ``frozen_logits`` (the logits once from an eval-mode
+forward; the default recomputes them every epoch in train mode, the base model's dropout live as WATS.py:147-149).
 """
 from __future__ import annotations
 
@@ -43,9 +50,11 @@ def accuracy(outputs: torch.Tensor, labels: torch.Tensor) -> float:
 
 class WATS(torch.nn.Module):
     def __init__(self, base_model, features, labels, adj, val_mask, *, k: int = 3, s: float = 0.8, X0=None,
-                 graph=None, wavelet_feats=None, verbose: bool = True, fused_head: bool = False):
+                 graph=None, wavelet_feats=None, verbose: bool = True, fused_head: bool = False,
+                 fused_training: bool = False, frozen_logits: bool = False, epochs: int = 250, train: bool = True):
         super().__init__()
         self.fused_head = bool(fused_head) and torch.cuda.is_available()
+        self.fused_training, self.frozen_logits, self.epochs = bool(fused_training), bool(frozen_logits), int(epochs)
         # WATS.py:91 picks cuda when available; the HIP feature path requires it.
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.base_model = base_model.to(self.device)
@@ -71,7 +80,8 @@ class WATS(torch.nn.Module):
         ).to(self.device)
         for para in self.net.parameters():
             para.requires_grad = True
-        self.calib_train()
+        if train:
+            self.calib_train()
 
     def temperatures(self) -> torch.Tensor:
         """Node-wise temperature ``log(exp(net(H)) + 1.1)`` (WATS.py:124-125)."""
@@ -96,12 +106,15 @@ class WATS(torch.nn.Module):
     def calib_train(self, patience: int = 10):
         """WATS.py:132-170: Adam(lr .01, wd 5e-4) on the temperature head only,
         NLL on the calibration nodes, <= 250 epochs, early stop after
-        ``patience`` non-improving epochs."""
+        ``patience`` non-improving epochs.  ``fused_training``: the same epochs as one HIP launch each
+        (``head.train_wats_head``)."""
+        if self.fused_training:
+            return self._fused_calib_train(patience)
         t = time.time()
         best_loss = float("inf")
         patience_counter = patience
         optimizer = torch.optim.Adam(self.net.parameters(), lr=0.01, weight_decay=5e-4)
-        for epoch in range(250):
+        for epoch in range(self.epochs):
             self.train()
             optimizer.zero_grad()
             output = self(self.x, self.adj)
@@ -123,6 +136,39 @@ class WATS(torch.nn.Module):
                 if self.verbose:
                     print(f"Early stopping at epoch {epoch}, best loss: {best_loss:.4f}")
                 break
+        return self
+
+    def _fused_calib_train(self, patience: int):
+        """The logits as ``scaling._Scaling._run_training`` takes them: once from an eval-mode forward
+        (``frozen_logits``), or per epoch in train mode, the base model's dropout live as WATS.py:147-149."""
+        from .gcn import SparseCompatibleGCN
+        from .head import train_wats_head
+        adj = self.adj
+        if isinstance(self.base_model, SparseCompatibleGCN) and torch.is_tensor(adj):
+            adj = self.base_model.operator(adj)        # built once, not per epoch
+        if self.frozen_logits:
+            self.eval()
+            with torch.no_grad():
+                logits = self.base_model(self.x, adj)
+        else:
+            def logits(epoch):
+                self.train()
+                with torch.no_grad():
+                    return self.base_model(self.x, adj)
+        t = time.time()
+        run = train_wats_head(self.wavelet_feats, logits, self.y, self.val_idx, self.net, epochs=self.epochs,
+                              patience=patience)
+        self.eval()
+        with torch.no_grad():
+            for p, v in zip(self.net.parameters(), run.params):
+                p.copy_(v.reshape(p.shape))
+        if self.verbose:
+            for e in range(run.epochs_run):
+                print(f"epoch: {e}", f"loss_calibration: {run.loss[e]:.4f}", f"acc_calibration: {run.acc[e]:.4f}",
+                      f"time: {time.time() - t:.4f}s")
+            if run.stop_epoch is not None:
+                print(f"Early stopping at epoch {run.stop_epoch}, best loss: {run.best_loss:.4f}")
+        self.training_run = run
         return self
 
     fit = calib_train

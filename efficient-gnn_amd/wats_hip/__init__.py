@@ -33,7 +33,7 @@ Calib_Random / Calib_RND / trial_logits (the reference's random baseline attacks
 the reference's own random stream and evaluated by one HIP launch, several targets in lock step),
 TemperatureScaling / VectorScaling / MatrixScaling / ETS / scaled_log_probs / train_scaling (the node-wise calibrators:
 their row maps fused in HIP, a training epoch -- loss, gradients, Adam, early stopping -- in one launch on a device
-state block), calibration_report / CalibrationReport / evaluate_calibration / evaluate_calibration_probs /
+state block; train_wats_head and WATS(fused_training=True): the same for WATS's temperature head), calibration_report / CalibrationReport / evaluate_calibration / evaluate_calibration_probs /
 reliability_curves / average_ece_many (the harness's evaluation step: accuracy, confidence, per-class and top-label
 ECE, NLL, Brier and the reliability curves from one fused HIP binning pass and one host read).
 """
@@ -62,7 +62,7 @@ from .gcn import (  # noqa: F401
     target_scores_from_grad,
     toggle_edges,
 )
-from .head import wats_head  # noqa: F401
+from .head import train_wats_head, wats_head  # noqa: F401
 from .ingest import DeviceCSR, edge_index_to_csr  # noqa: F401
 from .flips import FlippedAdjacency  # noqa: F401
 from .attack import (  # noqa: F401

@@ -125,6 +125,14 @@ SIGNATURES = {
     "wg_scale_epoch": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32,
                                       c_vp]),
     "wg_ets_label_probs": (ctypes.c_int, [c_i64, c_i64, c_i64] + [c_vp] * 6 + [c_vp]),
+    "wg_wats_train_max_params": (ctypes.c_int, []),
+    "wg_wats_train_chunk_rows": (ctypes.c_int, []),
+    "wg_wats_train_state_bytes": (ctypes.c_int, [c_i64, c_i32, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "wg_wats_train_state_init": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_i32, c_f64, c_f64]
+                                 + [c_vp] * 4 + [c_vp]),
+    "wg_wats_train_state_read": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64] + [c_vp] * 5 + [c_vp]),
+    "wg_wats_train_epoch": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64] + [c_vp] * 4
+                            + [c_i32, c_vp]),
     "wg_calib_chunk_rows": (ctypes.c_int, []),
     "wg_calib_max_rows": (ctypes.c_int, []),
     "wg_calib_max_classes": (ctypes.c_int, []),

@@ -1215,6 +1215,90 @@ int wg_ets_label_probs(int64_t n_total, int64_t n_rows, int64_t C, const float* 
                        double* p0y, double* p1y, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Section 8(f)-3: the WATS calibrator's calib_train (reference
+ * calibration/WATS.py:132-170) on the device (csrc/watstrain.hip), the design
+ * of wg_scale_epoch above.  The head is net = Linear(F, hid) - ReLU -
+ * Linear(hid, 1) on the wavelet features H (n_total, F) float32, row-major:
+ *   pre_j = b1_j + sum_f W1[j][f] H[f]     relu active iff pre_j > 0 (it hands
+ *   t = b2 + sum_j W2_j relu(pre_j)        a NaN on; pre_j == 0: gradient 0)
+ *   T = log(exp(t) + 1.1f),  out = log_softmax(z / T)      (WATS.py:124-130)
+ * with z = logits (n_total, C) float32.  W1 is (hid, F) row-major, b1 (hid),
+ * W2 (hid), b2 (1): P = hid * F + 2 hid + 1 parameters.
+ *
+ * wg_wats_train_epoch is one epoch in one launch over the listed rows (rows:
+ * int32 ids in [0, n_total), any order, repeats allowed; NULL means all rows,
+ * then n_rows == n_total), labels int64 (n_total) read at the listed ids: the
+ * forward, loss = -mean(out[r, y_r]), the gradients of all four tensors and
+ * the count of rows whose first maximal column is the label.  Rows are cut
+ * into fixed chunks of wg_wats_train_chunk_rows() (256) listed rows; each
+ * leaves one float64 partial vector: loss sum, correct count, then the P
+ * gradient sums (gW1 [hid][F], gb1, gW2, gb2).  The workgroup that arrives
+ * last (one relaxed agent-scope fetch_add per workgroup after its partials
+ * are drained; no workgroup waits on another) adds the partials in chunk
+ * order, divides by n_rows, takes torch's Adam step on all four tensors (lr,
+ * L2 weight decay g += wd * theta, betas 0.9 / 0.999, eps 1e-8,
+ * bias-corrected), updates best_loss, the patience counter and the stopped
+ * flag (1: patience ran out, 2: max_epochs reached; a NaN loss counts
+ * patience down), appends the loss and the accuracy to the traces and puts
+ * the arrival counter back.  A launch that finds stopped set returns without
+ * touching anything, so max_epochs launches may be enqueued back to back.
+ * n_workgroups = 0 picks the grid (one workgroup per chunk, at most 1024),
+ * 1 .. 1024 force it; the state's bits do not depend on it.
+ *
+ * The state is one device block of wg_wats_train_state_bytes bytes, 8-byte
+ * aligned: float64 master parameters and Adam moments, the step count,
+ * best_loss, the patience counter, the stopped flag, the epochs run, both
+ * traces and the chunk partials.  F, hid, C, max_epochs and max_rows of every
+ * wg_wats_train_epoch must be those the block was initialised with (n_rows <=
+ * max_rows is checked on the host, the rest on the device in the
+ * bounds-checked variant).  wg_wats_train_state_init fills it from the four
+ * float32 tensors; wg_wats_train_state_read copies the float32 rounding of
+ * the master parameters out (W1, b1, W2, b2: each nullable) and info
+ * (nullable) float64 [5 + 2 max_epochs] as wg_scale_state_read: stopped,
+ * epochs run, Adam steps, patience left, best loss, then the loss trace and
+ * the accuracy trace.
+ *
+ * Arithmetic: a wave per row, the hidden units on lanes; everything is
+ * float64, from the float64 master parameters and the float32 H / logits
+ * widened; the constant is (double)1.1f, the value the reference's float32
+ * tensor holds; every sum's order is fixed by the rows, F, hid and C; no
+ * float atomics: the same input gives the same bits on every grid.
+ *
+ * Checked before any device call: 1 <= hid <= 64, F >= 1, max_epochs >= 1, a
+ * NULL pointer not named nullable, n_rows == 0, n_rows > max_rows, rows NULL
+ * with n_rows != n_total, n_workgroups outside [0, 1024], patience < 1:
+ * WG_ERR_INVALID; P above wg_wats_train_max_params() (2048: four waves x P
+ * doubles of LDS, the bound of wg_wats_head_backward), C above
+ * wg_scale_max_c(0) (256), sizes above int32: WG_ERR_UNSUPPORTED.  Row ids,
+ * labels and the state's header are checked on the device in the
+ * bounds-checked variant only.
+ *
+ * queue is a HIP stream (NULL: the default stream), with the promise of the
+ * wg_scale_* section: the three device entry points are asynchronous,
+ * allocate nothing and may be captured: a replay of wg_wats_train_epoch is
+ * one more epoch on the state block (the last workgroup puts the arrival
+ * counter back), of wg_wats_train_state_init a fresh block.  These entries
+ * are held to that promise by tests/test_wats_train.py until a later change
+ * classifies them in the registry of tests/stream_cases.py and renames the
+ * parameter.
+ * ---------------------------------------------------------------------- */
+int wg_wats_train_max_params(void);
+int wg_wats_train_chunk_rows(void);
+int wg_wats_train_state_bytes(int64_t F, int32_t hid, int64_t max_epochs, int64_t max_rows,
+                              int64_t* bytes);
+int wg_wats_train_state_init(void* state, int64_t F, int32_t hid, int64_t C, int64_t max_epochs,
+                             int64_t max_rows, int32_t patience, double lr, double weight_decay,
+                             const float* W1, const float* b1, const float* W2, const float* b2,
+                             void* queue);
+int wg_wats_train_state_read(const void* state, int64_t F, int32_t hid, int64_t max_epochs,
+                             float* W1, float* b1, float* W2, float* b2, double* info,
+                             void* queue);
+int wg_wats_train_epoch(void* state, int64_t F, int32_t hid, int64_t C, int64_t max_epochs,
+                        int64_t max_rows, int64_t n_total, int64_t n_rows, const float* H,
+                        const float* logits, const int32_t* rows, const int64_t* labels,
+                        int32_t n_workgroups, void* queue);
+
+/* -------------------------------------------------------------------------
  * Section 8(f): the evaluation the harness runs after every calibrator and
  * every attack (csrc/calib.hip).  Replaces the host loops of
  * evaluate_calibration / evaluate_calibration_probs
